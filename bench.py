@@ -9,7 +9,23 @@ per GPU): every rank hashes its own 4096 chunks (global chunk ids
 4096*rank ..), no data-path collective -> weak scaling; the only
 collectives are the timing barrier and the max-over-ranks reduction.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel vs the HBM
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline
+figure needs and no more: it fills the batch, runs W untimed and N timed
+steps, and prints ONE JSON line on rank 0 with `value`, `ms_per_step` (wall
+milliseconds per timed step) and the figures that follow from the timed
+steps' own HIP events (`roofline`, `valu_ceiling`, `binding_limit`).
+--dump-outputs DIR writes what the last timed step left in its caller's
+digest buffers to DIR/digests.npy (float32, one row of 20 byte values per
+chunk; digests_rank<r>.npy under torchrun) before the line is printed.  The
+corpus is a fixed function of the chunk ids, so two runs with the same
+arguments hash the same bytes.
+
+--full adds every other leg below to the same line: the golden `parity` of
+the timed output, `strong`, `weak_config4`, the config 1 / 3 / 5, file,
+master-verify, verify-queue and one-chunk latency legs and `cpu_baseline`
+(each with its own switch, as before).
+
+The line carries `roofline` (dominant kernel vs the HBM
 peak, per-launch time from HIP events on the kernel's own stream; `traffic`
 from the committed rocprofv3 PMC pass, profiles/traffic_*.json),
 `binding_limit` (the limit that actually binds the workload's regime: at
@@ -152,7 +168,16 @@ def parse():
                     help="skip the config 1 / 3 / 5, file and master-verify legs (N = 1 only)")
     ap.add_argument("--file-chunks", type=int, default=16384,
                     help="512 KiB chunks of the file / master_verify legs' temp file (0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check their output against the golden digests and run "
+                         "every other leg (strong, weak config 4, configs 1 / 3 / 5, file, verify queue, "
+                         "latency, CPU baseline); off: the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the digests of the last timed step to DIR/digests.npy (float32)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def main():
@@ -239,24 +264,12 @@ def main():
     kern_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in evs]))
     elapsed, kern_ms = shard.max_over_ranks([t1 - t0, kern_ms], device=cdev)
 
-    # ---- parity of the timed output (every rank, against the reference) ----
-    # Checked with the standard library's SHA-1 (hashlib), independent of
-    # both the engine and oracle/: the digest-of-digests of a 4096-chunk
-    # range against the reference-generated golden aggregate, otherwise a
-    # sample of chunks re-hashed from the device buffer's own bytes.
-    golden = json.load(open(os.path.join(ROOT, "tests/golden/golden.json")))
-    parity = True
-    for p in range(P):
-        got = digs[p].cpu().numpy()
-        b = first // n + p  # index of this batch's 4096-chunk range
-        if n == 4096 and L == CHUNK_LEN and b < len(golden["weak4096"]):
-            parity &= hashlib.sha1(got.tobytes()).hexdigest() == golden["weak4096"][b]
-        else:
-            idx = np.unique(np.linspace(0, n - 1, min(n, 16)).astype(np.int64))
-            for i in idx:
-                chunk = bufs[p][int(i) * L:(int(i) + 1) * L].cpu().numpy().tobytes()
-                parity &= hashlib.sha1(chunk).digest() == got[int(i)].tobytes()
-    parity = shard.all_ranks_ok(parity, device=cdev)
+    if a.dump_outputs:
+        _dump_outputs(a.dump_outputs, digs, rank if use_pg else None, world)
+    golden = parity = None
+    if a.full:
+        golden = json.load(open(os.path.join(ROOT, "tests/golden/golden.json")))
+        parity = shard.all_ranks_ok(_timed_parity(golden, bufs, digs, first, n, L), device=cdev)
 
     ms_per_step = elapsed / a.steps * 1e3
     total_bytes = world * n * L
@@ -343,6 +356,56 @@ def main():
     # free the config-2 buffers before the strong leg's 128 GiB / N
     del bufs, digs
     torch.cuda.empty_cache()
+    if a.full:
+        _full_legs(a, result, pkg, shard, torch, dist, world, rank, cdev, golden, dev, n, L)
+    else:
+        del result["parity"]  # checked under --full only
+    if use_pg:
+        result["config"]["control_plane"] = f"torch.distributed {backend}, world {world}"
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if use_pg:
+        dist.destroy_process_group()
+
+
+def _timed_parity(golden, bufs, digs, first, n, L) -> bool:
+    """Parity of the timed output (this rank's, against the reference).
+    Checked with the standard library's SHA-1 (hashlib), independent of
+    both the engine and oracle/: the digest-of-digests of a 4096-chunk
+    range against the reference-generated golden aggregate, otherwise a
+    sample of chunks re-hashed from the device buffer's own bytes."""
+    parity = True
+    for p in range(len(digs)):
+        got = digs[p].cpu().numpy()
+        b = first // n + p  # index of this batch's 4096-chunk range
+        if n == 4096 and L == CHUNK_LEN and b < len(golden["weak4096"]):
+            parity &= hashlib.sha1(got.tobytes()).hexdigest() == golden["weak4096"][b]
+        else:
+            idx = np.unique(np.linspace(0, n - 1, min(n, 16)).astype(np.int64))
+            for i in idx:
+                chunk = bufs[p][int(i) * L:(int(i) + 1) * L].cpu().numpy().tobytes()
+                parity &= hashlib.sha1(chunk).digest() == got[int(i)].tobytes()
+    return parity
+
+
+DUMP_CAP_BYTES = 64 << 20  # of .npy data per --dump-outputs directory
+
+
+def _dump_outputs(path: str, digs, rank, world: int = 1) -> None:
+    """The digest buffers as the timed steps left them (batch 0 .. P-1 in
+    order, one row per chunk) as float32.  Above the cap (shared equally by
+    the ranks) a fixed, seeded sample of rows, in index order."""
+    got = np.concatenate([d.cpu().numpy() for d in digs]).astype(np.float32)
+    cap_rows = (DUMP_CAP_BYTES // world - 4096) // (got.shape[1] * 4)
+    if got.shape[0] > cap_rows:
+        keep = np.sort(np.random.default_rng(0x5EED).choice(got.shape[0], cap_rows, replace=False))
+        got = got[keep]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "digests.npy" if rank is None else f"digests_rank{rank}.npy"), got)
+
+
+def _full_legs(a, result, pkg, shard, torch, dist, world, rank, cdev, golden, dev, n, L) -> None:
+    """Every leg beyond the timed steps (--full), added to `result`."""
     if a.strong_total > 0:
         result["strong"] = _strong_leg(pkg, shard, torch, dist, world, rank, cdev, a, golden)
     if a.weak4_chunks > 0:
@@ -378,7 +441,13 @@ def main():
                         result["master_verify"] = {"error": repr(e)[:300]}
         if rank == 0 and world == 1 and not a.no_latency:
             result["latency_one_chunk"] = _latency_one_chunk(dev)
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        cpu_leg = rank == 0 and world == 1 and not a.no_cpu_baseline
+        if cpu_leg:
+            from oracle import oracle as O
+            if O.ref_lib() is None:  # a tree built without the reference's sources: say so, time nothing
+                result["cpu_baseline"] = {"error": "oracle/_ref not built (make -C oracle ref)"}
+                cpu_leg = False
+        if cpu_leg:
             from oracle import oracle as O  # the CPU baseline leg only: the reference sha.c, timed
             result["cpu_baseline"] = _cpu_baseline(O, n, L, golden, a.cpu_threads or None)
             if "latency_one_chunk" in result:
@@ -411,12 +480,6 @@ def main():
     finally:
         if fpath and os.path.exists(fpath):
             os.unlink(fpath)
-    if use_pg:
-        result["config"]["control_plane"] = f"torch.distributed {backend}, world {world}"
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if use_pg:
-        dist.destroy_process_group()
 
 
 def _time_launches(pkg, torch, buf, L, n, dig, stream, steps, warmup):

@@ -32,7 +32,7 @@ def _free_port():
 def test_bench_two_ranks_weak_and_strong(pkg):
     env = dict(os.environ, SHA1_BENCH_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--full",
            "--steps", "3", "--warmup", "1", "--strong-steps", "1", "--no-latency", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -59,7 +59,7 @@ def test_bench_rccl_control_plane_one_rank(pkg):
     env = dict(os.environ, SHA1_BENCH_FORCE_PG="1")
     env.pop("SHA1_BENCH_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full",
            "--steps", "3", "--warmup", "1", "--strong-steps", "1", "--no-latency", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]

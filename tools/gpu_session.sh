@@ -39,7 +39,7 @@ for s in $STEPS; do
                -k test_config1_make_chunks_cli --timeout 200 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     sweep) run sweep 600 python tools/sweep.py --chunks 1024,4096,16384,65536,131072 --rounds 2 --out "$OUT/sweep.json" ;;
-    bench) run bench 600 python bench.py --steps 10 --warmup 2 ;;
+    bench) run bench 600 python bench.py --full --steps 10 --warmup 2 ;;
     prof)  run rocprof 900 bash tools/profile_bench.sh $TAG ;;
     pmc)   run pmc 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- \
                python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
@@ -66,9 +66,9 @@ for s in $STEPS; do
              run shardprod 300 python tools/sweep.py --chunks 32768,4096 --kernels split --rounds 5 --burst 8 \
                  --out "$OUT/shardprod.json" ;;
     rehearse2) SHA1_BENCH_DIST_BACKEND=gloo run rehearse2 600 python -m torch.distributed.run --nnodes=1 \
-                   --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 ;;
+                   --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --full --steps 10 --warmup 2 ;;
     rehearse4) SHA1_BENCH_DIST_BACKEND=gloo run rehearse4 600 python -m torch.distributed.run --nnodes=1 \
-                   --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 4 --steps 10 --warmup 2 ;;
+                   --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 4 --full --steps 10 --warmup 2 ;;
     vqbench) run vqbench 600 python tools/vq_bench.py --chunks 16384 --batches 64,256,1024 --reps 3 \
                  --out "$OUT/vq_bench.json" ;;
     vqhost1) run vqhost1 300 python tools/vq_bench.py --chunks 4096 --batches 64 --reps 2 \

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per (kernel, grid size) dispatch statistics of a rocprofv3 kernel trace
-(run_kernel_trace.csv): bench.py runs config 2 and then its other legs
+(run_kernel_trace.csv): bench.py --full runs config 2 and then its other legs
 (config 5, config 3, the one-chunk latency, ...) whose launches share kernel
 names with config 2's, so the stats CSV's per-name average mixes them; the
 timed config-2 launches are the ones with config 2's grid.
