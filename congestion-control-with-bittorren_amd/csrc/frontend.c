@@ -85,6 +85,14 @@ static int fail(int code, const char *fmt, ...) {
     X(long, vq_poll, (void *, uint64_t *, uint8_t *, size_t, int))                                \
     X(size_t, vq_pending, (const void *))                                                         \
     X(void, vq_destroy, (void *))                                                                 \
+    X(void *, pv_create, (size_t, uint32_t))                                                      \
+    X(void *, pv_open, (void *, uint32_t, const uint8_t *, uint64_t))                             \
+    X(int, pv_advance, (void *, void *, uint32_t))                                                \
+    X(int, pv_hashed, (void *, const void *, uint32_t *))                                         \
+    X(long, pv_poll, (void *, uint64_t *, uint8_t *, uint8_t *, size_t, int))                     \
+    X(int, pv_close, (void *, void *))                                                            \
+    X(size_t, pv_pending, (const void *))                                                         \
+    X(void, pv_destroy, (void *))                                                                 \
     X(int, device_count, (void))                                                                  \
     X(int, set_device, (int))                                                                     \
     X(int, device_pci_bus_id, (int, char *, size_t))                                              \
@@ -752,4 +760,60 @@ FE_API void sha1chunk_vq_destroy(sha1chunk_vq *q) {
     free(q->mis);
     pthread_mutex_destroy(&q->mu);
     free(q);
+}
+
+/* ----------------------------------------------------- progressive verifier -- */
+/* A sha1chunk_pv is the backend's object itself: there is no host path
+ * (SHA1CHUNK_HOST_SMALL does not apply), every call is a forward. */
+FE_API sha1chunk_pv *sha1chunk_pv_create(size_t sessions, uint32_t max_chunk_len) {
+    if (sessions == 0) {
+        fail(SHA1CHUNK_EINVAL, "pv: at least one session required");
+        return NULL;
+    }
+    if (backend_dev()) return NULL;
+    void *p = BE.pv_create(sessions, max_chunk_len);
+    if (!p) fail(SHA1CHUNK_ENOMEM, "%s", BE.last_error());
+    return (sha1chunk_pv *)p;
+}
+
+FE_API void *sha1chunk_pv_open(sha1chunk_pv *p, uint32_t len, const uint8_t expected[20], uint64_t tag) {
+    if (!p || !expected) {
+        fail(SHA1CHUNK_EINVAL, "pv: null argument");
+        return NULL;
+    }
+    if (backend_dev()) return NULL;
+    void *buf = BE.pv_open(p, len, expected, tag);
+    if (!buf) fail(SHA1CHUNK_ENOMEM, "%s", BE.last_error());
+    return buf;
+}
+
+FE_API int sha1chunk_pv_advance(sha1chunk_pv *p, void *buf, uint32_t ready) {
+    if (!p || !buf) return fail(SHA1CHUNK_EINVAL, "pv: null argument");
+    FORWARD(int, pv_advance(p, buf, ready));
+}
+
+FE_API int sha1chunk_pv_hashed(sha1chunk_pv *p, const void *buf, uint32_t *bytes) {
+    if (!p || !buf || !bytes) return fail(SHA1CHUNK_EINVAL, "pv: null argument");
+    FORWARD(int, pv_hashed(p, buf, bytes));
+}
+
+FE_API long sha1chunk_pv_poll(sha1chunk_pv *p, uint64_t *tags, uint8_t *mismatch, uint8_t *digests, size_t max,
+                              int wait) {
+    if (!p || (max && (!tags || !mismatch))) return fail(SHA1CHUNK_EINVAL, "pv: null argument");
+    FORWARD(long, pv_poll(p, tags, mismatch, digests, max, wait));
+}
+
+FE_API int sha1chunk_pv_close(sha1chunk_pv *p, void *buf) {
+    if (!p || !buf) return fail(SHA1CHUNK_EINVAL, "pv: null argument");
+    FORWARD(int, pv_close(p, buf));
+}
+
+FE_API size_t sha1chunk_pv_pending(const sha1chunk_pv *p) {
+    if (!p || backend()) return 0;
+    return BE.pv_pending(p);
+}
+
+FE_API void sha1chunk_pv_destroy(sha1chunk_pv *p) {
+    if (!p || backend()) return;
+    BE.pv_destroy(p);
 }

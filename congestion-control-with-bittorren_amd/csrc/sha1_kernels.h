@@ -91,6 +91,36 @@ struct VqDrainArgs {
 };
 hipError_t launch_vq_drain(const VqDrainArgs& Q, uint32_t grid, hipStream_t st);
 
+// Progressive verify (sha1_progress.hip; host side in sha1_pv.hip, the
+// sha1chunk_pv object).  One launch advances any number of receive sessions:
+// work-list entry e says which bytes of its session became final since the
+// session's last entry, and lane e hashes exactly those.  The session
+// buffers, the work list, the expected digests and the results live in
+// pinned host memory (read and written over PCIe); only the midstates are in
+// device memory.
+struct PvEntry {
+    uint32_t session;  // index of the session (buffer at data + session * stride)
+    uint32_t from;     // bytes hashed by the session's earlier entries, a multiple of 64
+    uint32_t upto;     // final bytes: a multiple of 64, or len when `final`
+    uint32_t len;      // the chunk's length
+    uint32_t final;    // nonzero: upto == len; pad, compare, publish
+    uint32_t gen;      // the session's generation, published in done[session]
+    uint32_t pad[2];   // 32 bytes: two 16-byte loads per lane
+};
+struct PvArgs {
+    const uint8_t* data;       // host: sessions x stride bytes, 128-byte aligned buffers
+    uint64_t stride;
+    const PvEntry* work;       // host: n entries, at most one per session
+    uint32_t n;
+    uint32_t sessions;
+    uint32_t* state;           // device: 5 midstate words per session
+    const uint32_t* expected;  // host: 8 words per session, the first 5 the expected digest
+    uint32_t* result;          // host: 8 words per session: digest (5), mismatch (1)
+    uint32_t* done;            // host: per session, its generation once the result is written
+};
+// depth: 64-byte blocks of each lane in flight ahead of its compression (2, 4 or 8).
+hipError_t launch_progress(const PvArgs& P, int depth, hipStream_t st);
+
 hipError_t launch_synth(uint8_t* dst, const uint64_t* off, const uint32_t* lens, uint32_t ulen,
                         uint64_t first, uint64_t count, uint64_t seed, hipStream_t st);
 hipError_t launch_compare(const uint8_t* dig, const uint8_t* exp, uint32_t n, uint8_t* mismatch,

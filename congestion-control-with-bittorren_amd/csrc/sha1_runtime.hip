@@ -39,6 +39,7 @@
 #include "../../include/sha1chunk.h"
 #include "part_pool.hpp"
 #include "sha1_kernels.h"
+#include "sha1_runtime_internal.h"
 
 namespace {
 using s1host::PartPool;
@@ -149,13 +150,7 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(SHA1CHUNK_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                                  \
-    } while (0)
+// HIP_TRY: sha1_runtime_internal.h
 
 constexpr size_t kAlign = 128;  // device layout: every chunk starts on a 128-B line
 // Stream (file) pipeline: a ring of slots, each read into pinned memory,
@@ -2570,3 +2565,24 @@ void s1be_vq_destroy(void* qv) {
 }
 
 }  // extern "C"
+
+// What sha1_pv.hip shares with this file (sha1_runtime_internal.h).
+namespace s1rt {
+int fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return ::fail(code, "%s", buf);
+}
+int acquire_device(int* hip_id, int* cus) {
+    Device* D;
+    if (int rc = get_device(&D)) return rc;
+    *hip_id = D->id;
+    *cus = D->cus;
+    return SHA1CHUNK_OK;
+}
+unsigned pinned_ring_flags() { return ring_flags(); }
+int stream_create(hipStream_t* s) { return vq_stream_create(s); }
+}  // namespace s1rt

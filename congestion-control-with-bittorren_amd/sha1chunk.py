@@ -108,6 +108,14 @@ _SIGNATURES = [
     ("sha1chunk_vq_poll", C.c_long, [_vp, _u64p, _u8p, C.c_size_t, C.c_int]),
     ("sha1chunk_vq_pending", C.c_size_t, [_vp]),
     ("sha1chunk_vq_destroy", None, [_vp]),
+    ("sha1chunk_pv_create", C.c_void_p, [C.c_size_t, C.c_uint32]),
+    ("sha1chunk_pv_open", C.c_void_p, [_vp, C.c_uint32, _u8p, C.c_uint64]),
+    ("sha1chunk_pv_advance", C.c_int, [_vp, _vp, C.c_uint32]),
+    ("sha1chunk_pv_hashed", C.c_int, [_vp, _vp, _u32p]),
+    ("sha1chunk_pv_poll", C.c_long, [_vp, _u64p, _u8p, _u8p, C.c_size_t, C.c_int]),
+    ("sha1chunk_pv_close", C.c_int, [_vp, _vp]),
+    ("sha1chunk_pv_pending", C.c_size_t, [_vp]),
+    ("sha1chunk_pv_destroy", None, [_vp]),
     ("sha1chunk_device_count", C.c_int, []),
     ("sha1chunk_set_device", C.c_int, [C.c_int]),
     ("sha1chunk_get_device", C.c_int, []),
@@ -398,6 +406,81 @@ class VerifyQueue:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+class ProgressiveVerifier:
+    """Verify chunks while they are received (sha1chunk_pv, include/
+    sha1chunk.h): open() hands out a session's buffer -- the peer's
+    recv_session->data -- as a `Reservation`; advance(r, ready) states that
+    bytes [0, ready) are final (after cumulative_ack: min(len, 1484 *
+    last_packet_acked)) and the device hashes them while the rest arrives;
+    poll() yields (tag, mismatch) as verify_hash returns it, with the
+    computed digests too under with_digests=True."""
+
+    def __init__(self, sessions: int = 64, max_chunk_len: int = CHUNK_LEN):
+        self._p = lib().sha1chunk_pv_create(sessions, max_chunk_len)
+        if not self._p:
+            raise Sha1ChunkError(ENODEV if device_count() == 0 else EINVAL, "sha1chunk_pv_create",
+                                 lib().sha1chunk_last_error().decode(errors="replace"))
+
+    def open(self, length: int, expected: bytes | str, tag: int) -> "Reservation":
+        """A session for a chunk of `length` bytes: fill `.view` in place."""
+        exp = bytes.fromhex(expected) if isinstance(expected, str) else bytes(expected)
+        if len(exp) != DIGEST_LEN:
+            raise ValueError("expected digest must be 20 bytes / 40 hex chars")
+        e = np.frombuffer(exp, np.uint8)
+        p = lib().sha1chunk_pv_open(self._p, length, _np_ptr(e), tag)
+        if not p:
+            raise Sha1ChunkError(ENOMEM, "sha1chunk_pv_open",
+                                 lib().sha1chunk_last_error().decode(errors="replace"))
+        return Reservation(p, length)
+
+    def advance(self, r: "Reservation", ready: int) -> None:
+        """Bytes [0, ready) of the session are final; ready == length completes it."""
+        _check(lib().sha1chunk_pv_advance(self._p, r.ptr, ready), "sha1chunk_pv_advance")
+
+    def hashed(self, r: "Reservation") -> int:
+        """Bytes of the session the device has confirmed hashed."""
+        n = C.c_uint32(0)
+        _check(lib().sha1chunk_pv_hashed(self._p, r.ptr, C.byref(n)), "sha1chunk_pv_hashed")
+        return n.value
+
+    def poll(self, wait: bool = False, max_results: int = 1 << 12, with_digests: bool = False):
+        """Finished [(tag, mismatch)], or [(tag, mismatch, digest)] with_digests."""
+        tags = np.zeros(max_results, np.uint64)
+        mism = np.zeros(max_results, np.uint8)
+        dig = np.zeros((max_results, DIGEST_LEN), np.uint8) if with_digests else None
+        n = _check(lib().sha1chunk_pv_poll(self._p, _np_ptr(tags, _u64p), _np_ptr(mism),
+                                           _np_ptr(dig) if with_digests else None, max_results,
+                                           1 if wait else 0), "sha1chunk_pv_poll")
+        if with_digests:
+            return [(int(tags[i]), int(mism[i]), dig[i].tobytes()) for i in range(n)]
+        return [(int(tags[i]), int(mism[i])) for i in range(n)]
+
+    def close(self, r: "Reservation") -> None:
+        """Free a session: before completion (dropped) or after its result."""
+        _check(lib().sha1chunk_pv_close(self._p, r.ptr), "sha1chunk_pv_close")
+
+    @property
+    def pending(self) -> int:
+        return int(lib().sha1chunk_pv_pending(self._p))
+
+    def destroy(self) -> None:
+        if self._p:
+            lib().sha1chunk_pv_destroy(self._p)
+            self._p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.destroy()
+
+    def __del__(self):
+        try:
+            self.destroy()
         except Exception:
             pass
 

@@ -265,6 +265,89 @@ long sha1chunk_vq_poll(sha1chunk_vq *q, uint64_t *tags, uint8_t *mismatch, size_
 size_t sha1chunk_vq_pending(const sha1chunk_vq *q);
 void sha1chunk_vq_destroy(sha1chunk_vq *q);
 
+/* ---- Progressive verify: hash a chunk while it is received ---------------
+ * Every entry point above starts a chunk's hash when the chunk is complete,
+ * so its verdict comes one serial chain (8192 compressions for 512 KiB,
+ * ~6 ms on a GPU lane) after the last packet.  SHA-1 is serial inside a
+ * message, so that chain cannot be shortened -- but it need not wait for the
+ * last packet.  The reference's reliable UDP layer already knows which bytes
+ * are final: cumulative_ack (reliable_udp.c:300-324) maintains
+ * last_packet_acked, so bytes [0, 1484 x last_packet_acked) of
+ * recv_session->data no longer change, while packets above that mark may
+ * still land out of order (reliable_udp.c:331-350).  A progressive verifier
+ * hashes the final bytes as the mark moves; after the last packet only the
+ * last <= 1484 bytes (24 blocks) and the padding remain.
+ *
+ * create() makes `sessions` receive buffers of max_chunk_len bytes, each
+ * starting on a 128-byte line, in pinned host memory that the device reads
+ * directly (allocated like the persistent queue's PCIe-read ring), and one
+ * private stream, on the device current at the call.  NULL on failure
+ * (sha1chunk_last_error() says why); without a device there is no object:
+ * no CPU fallback, and SHA1CHUNK_HOST_SMALL does not apply -- this object
+ * always runs on the gfx950 kernel (csrc/sha1_progress.hip).
+ *
+ * open() starts a chunk of len bytes with its expected digest and a tag and
+ * returns the session's buffer -- the peer's recv_session->data
+ * (reliable_udp.c:121) -- or NULL when every session is in use or
+ * len > max_chunk_len.
+ *
+ * advance(buf, ready) states that bytes [0, ready) are final: they will not
+ * change again (rewriting them with the same contents, as a duplicate packet
+ * does, is fine).  Bytes at and above ready may be written in any order and
+ * overwritten freely; the device never reads them.  ready never decreases,
+ * never exceeds len, and may move by any amount, 0 and 1 included.  The
+ * session is complete when ready == len (for len == 0: advance(buf, 0)).
+ * The call never waits for the device.
+ *
+ * hashed() reports how many bytes of the session the device has confirmed
+ * hashed: a multiple of 64, or len once the verdict exists.
+ *
+ * poll() returns finished (tag, mismatch) pairs, mismatch as verify_hash
+ * returns it (0 = match, 1 = mismatch -> re-GET), each tag exactly once, and
+ * with digests != NULL each computed digest, 20 bytes per result (job.c:219-
+ * 220 prints both hashes on a mismatch).  wait != 0 blocks until every
+ * session completed before the call has its result.
+ *
+ * close() frees the session: before completion (the chunk is dropped, no
+ * result is delivered) or after it (a verdict not yet polled still comes).
+ * The buffer is not handed out again while an enqueued launch refers to it.
+ * pending() counts completed sessions whose result poll() has not returned.
+ *
+ * Launch policy: advance() records the mark; advance(), hashed() and poll()
+ * enqueue one kernel when fewer than two launches of the object are
+ * outstanding (an event per launch slot, queried, never waited for) and
+ * there is work -- a session with a new whole 64-byte block, or a completed
+ * one.  While two launches are outstanding work accumulates and the next
+ * launch takes all of it, so the launch rate is bounded by the kernel's time
+ * with no threshold to tune.  No helper thread, no persistent kernel: every
+ * kernel ends on its own and none waits on host memory.
+ *
+ * Errors: SHA1CHUNK_EINVAL for a buffer that is not an open session's, a
+ * mark that moves back or beyond len, and an advance after completion.
+ * Every call takes the object's lock, so several receive threads may share
+ * one object; destroy() must not overlap any other call.
+ *
+ * Measured on MI355X (tools/pv_latency_bench, profiles/pv_latency.jsonl,
+ * DESIGN.md section 6): a 512 KiB chunk fed in its 354 packets with the
+ * hashing keeping up has its verdict 28.7-31.4 us (median of 24 chunks, six
+ * runs; every chunk 27-35) after the final advance, against 6.05 ms for the
+ * same chunk through sha1chunk_vq_submit.  That needs the chunk to arrive
+ * slower than one lane hashes it (~50 MB/s from pinned memory; one launch
+ * per packet up to 32 MB/s): fed all at once its verdict comes 10.2-10.8 ms
+ * after the last byte, one lane's whole chain, more than the queue's.  64 /
+ * 256 sessions fed at once hash at 167-476 / 141-174 MB/s in aggregate (each
+ * lane's 16-byte reads over PCIe are the bound). */
+typedef struct sha1chunk_pv sha1chunk_pv;
+sha1chunk_pv *sha1chunk_pv_create(size_t sessions, uint32_t max_chunk_len);
+void *sha1chunk_pv_open(sha1chunk_pv *p, uint32_t len, const uint8_t expected[20], uint64_t tag);
+int sha1chunk_pv_advance(sha1chunk_pv *p, void *buf, uint32_t ready);
+int sha1chunk_pv_hashed(sha1chunk_pv *p, const void *buf, uint32_t *bytes);
+long sha1chunk_pv_poll(sha1chunk_pv *p, uint64_t *tags, uint8_t *mismatch, uint8_t *digests,
+                       size_t max, int wait);
+int sha1chunk_pv_close(sha1chunk_pv *p, void *buf);
+size_t sha1chunk_pv_pending(const sha1chunk_pv *p);
+void sha1chunk_pv_destroy(sha1chunk_pv *p);
+
 /* Device management. */
 int sha1chunk_device_count(void);
 int sha1chunk_set_device(int device);
