@@ -93,6 +93,8 @@ static int fail(int code, const char *fmt, ...) {
     X(int, pv_close, (void *, void *))                                                            \
     X(size_t, pv_pending, (const void *))                                                         \
     X(void, pv_destroy, (void *))                                                                 \
+    X(int, burst_advance, (void *, void *const *, const uint32_t *, size_t, size_t *))            \
+    X(int, progress_stats, (void *, void *, size_t))                                              \
     X(int, device_count, (void))                                                                  \
     X(int, set_device, (int))                                                                     \
     X(int, device_pci_bus_id, (int, char *, size_t))                                              \
@@ -816,4 +818,16 @@ FE_API size_t sha1chunk_pv_pending(const sha1chunk_pv *p) {
 FE_API void sha1chunk_pv_destroy(sha1chunk_pv *p) {
     if (!p || backend()) return;
     BE.pv_destroy(p);
+}
+
+FE_API int sha1chunk_burst_advance(sha1chunk_pv *p, void *const *bufs, const uint32_t *ready, size_t n,
+                                   size_t *applied) {
+    if (applied) *applied = 0;
+    if (!p || (n && (!bufs || !ready))) return fail(SHA1CHUNK_EINVAL, "pv: null argument");
+    FORWARD(int, burst_advance(p, bufs, ready, n, applied));
+}
+
+FE_API int sha1chunk_progress_stats(sha1chunk_pv *p, sha1chunk_progress_stats_t *out, size_t size) {
+    if (!p || !out) return fail(SHA1CHUNK_EINVAL, "pv: null argument");
+    FORWARD(int, progress_stats(p, out, size));
 }

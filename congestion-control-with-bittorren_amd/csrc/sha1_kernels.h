@@ -117,9 +117,13 @@ struct PvArgs {
     const uint32_t* expected;  // host: 8 words per session, the first 5 the expected digest
     uint32_t* result;          // host: 8 words per session: digest (5), mismatch (1)
     uint32_t* done;            // host: per session, its generation once the result is written
+    const uint8_t* dummy;      // device: 64 bytes no session owns (shared kernel: a slot with nothing to load)
 };
 // depth: 64-byte blocks of each lane in flight ahead of its compression (2, 4 or 8).
 hipError_t launch_progress(const PvArgs& P, int depth, hipStream_t st);
+// The same work with the bulk blocks' loads shared across the wave, four
+// lanes per entry (sha1_progress_shared.hip): for many sessions at once.
+hipError_t launch_progress_shared(const PvArgs& P, hipStream_t st);
 
 hipError_t launch_synth(uint8_t* dst, const uint64_t* off, const uint32_t* lens, uint32_t ulen,
                         uint64_t first, uint64_t count, uint64_t seed, hipStream_t st);

@@ -1,6 +1,7 @@
 // sha1_pv.hip -- host side of the progressive verifier (sha1chunk_pv,
-// include/sha1chunk.h; kernel: sha1_progress.hip).  Exports s1be_pv_* to the
-// front end, nothing else.
+// include/sha1chunk.h; kernels: sha1_progress.hip, one lane per session, and
+// sha1_progress_shared.hip, loads shared across the wave).  Exports s1be_pv_*,
+// s1be_burst_advance and s1be_progress_stats to the front end, nothing else.
 //
 // The object owns `sessions` receive buffers in pinned host memory, one
 // private stream and two launch slots.  advance() only records a session's
@@ -15,7 +16,7 @@
 //   launch   with a launch slot free and work pending (a session with a new
 //            whole block, or a completed one), one kernel takes all of it:
 //            the work list goes into the slot's part of a pinned ring, one
-//            entry per session.
+//            entry per session.  Which kernel: SHA1CHUNK_PV_KERNEL (pv_pick).
 // While both slots are outstanding work accumulates, so the launch rate is
 // bounded by the kernel's time, with no threshold to tune.  The host owns
 // the byte accounting (from / upto of every entry); the device only the
@@ -46,6 +47,16 @@ using s1rt::fail;
 
 constexpr size_t kAlign = 128;  // every session buffer starts on a 128-byte line
 constexpr int kLaunchSlots = 2;
+enum { kKernelAuto = 0, kKernelLane = 1, kKernelShared = 2 };
+// `auto` takes the shared-load kernel for a work list with at least this
+// many entries that carry a whole block; 0: never.  64, a whole wave: the
+// smallest session count measured (4, 16, 64, 256; DESIGN.md section 6,
+// profiles/pv_shared.jsonl) at which the shared kernel's median passed the
+// lane kernel's by more than the lane kernel's own spread -- 1531 against
+// 217 MB/s (194-280) fed per call; at 16 both hash at the lanes' compute
+// rate, 820 against 807 (736-861).  It counts one launch's entries: fewer
+// than 64 sessions with a new block stay on the lane kernel.
+constexpr uint32_t kSharedThreshold = 64;
 
 inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -96,7 +107,9 @@ struct Pv {
     uint32_t* result = nullptr;    // 8 words per session
     uint32_t* done = nullptr;      // 1 word per session
     PvEntry* work = nullptr;       // kLaunchSlots x sessions entries
-    uint32_t* state = nullptr;     // device: 5 words per session
+    uint32_t* state = nullptr;     // device: 5 words per session, then the 64-byte dummy line
+    const uint8_t* dummy = nullptr;
+    int kernel = kKernelAuto;      // SHA1CHUNK_PV_KERNEL
     hipStream_t stream = nullptr;
     PvLaunch launch[kLaunchSlots];
     std::vector<PvSession> ses;
@@ -109,7 +122,7 @@ struct Pv {
     int error = 0;  // a HIP failure in pump(): every later call reports it
     std::string error_text;
     bool stats = false;
-    uint64_t n_launch = 0, n_entries = 0, n_blocks = 0;
+    uint64_t n_launch = 0, n_launch_shared = 0, n_entries = 0, n_blocks = 0;
 };
 
 void pv_free_session(Pv* p, uint32_t s) {
@@ -137,6 +150,13 @@ void pv_mark_dirty(Pv* p, uint32_t s) {
     if (S.dirty) return;
     S.dirty = true;
     p->dirty.push_back(s);
+}
+
+// The kernel of a launch of n entries, `with_block` of them with a whole block.
+bool pv_pick_shared(const Pv* p, uint32_t n, uint32_t with_block) {
+    if (p->kernel != kKernelAuto) return p->kernel == kKernelShared;
+    // a lone session's launches stay what they were
+    return n > 1 && kSharedThreshold != 0 && with_block >= kSharedThreshold;
 }
 
 // Caller holds p->mu and has made p->dev current.  Never blocks.
@@ -188,7 +208,7 @@ int pv_pump(Pv* p) {
     if (k < 0) return SHA1CHUNK_OK;
     PvLaunch& L = p->launch[k];
     PvEntry* W = p->work + size_t(k) * p->sessions;
-    uint32_t n = 0;
+    uint32_t n = 0, with_block = 0;
     for (const uint32_t s : p->dirty) {
         PvSession& S = p->ses[s];
         S.dirty = false;
@@ -205,6 +225,7 @@ int pv_pump(Pv* p) {
         W[n++] = E;
         L.items.push_back({s, S.gen, upto});
         p->n_blocks += (upto - S.issued) / 64u;
+        with_block += upto - S.issued >= 64u ? 1u : 0u;
         S.issued = S.complete ? S.len : upto;
         ++S.refs;
         if (S.complete) {
@@ -226,11 +247,15 @@ int pv_pump(Pv* p) {
     A.expected = p->expected;
     A.result = p->result;
     A.done = p->done;
-    hipError_t e = launch_progress(A, p->depth, p->stream);
-    if (e != hipSuccess) return pv_hip_error(p, e, "sha1_progress_kernel launch");
+    A.dummy = p->dummy;
+    const bool shared = pv_pick_shared(p, n, with_block);
+    hipError_t e = shared ? launch_progress_shared(A, p->stream) : launch_progress(A, p->depth, p->stream);
+    if (e != hipSuccess)
+        return pv_hip_error(p, e, shared ? "sha1_progress_shared_kernel launch" : "sha1_progress_kernel launch");
     if ((e = hipEventRecord(L.ev, p->stream)) != hipSuccess) return pv_hip_error(p, e, "hipEventRecord");
     L.busy = true;
     ++p->n_launch;
+    p->n_launch_shared += shared ? 1u : 0u;
     p->n_entries += n;
     return SHA1CHUNK_OK;
 }
@@ -276,6 +301,8 @@ void pv_release(Pv* p) {
 
 extern "C" {
 
+const char* s1be_last_error(void);  // sha1_runtime.hip
+
 void* s1be_pv_create(size_t sessions, uint32_t max_chunk_len) {
     if (sessions == 0 || sessions > (1u << 20)) {
         fail(SHA1CHUNK_EINVAL, "pv: 1..2^20 sessions required");
@@ -299,6 +326,21 @@ void* s1be_pv_create(size_t sessions, uint32_t max_chunk_len) {
             return nullptr;
         }
     }
+    // which kernel a launch takes: auto (pv_pick_shared), or one of them for
+    // every launch, single-entry work lists included
+    if (const char* e = getenv("SHA1CHUNK_PV_KERNEL")) {
+        if (!strcmp(e, "auto")) {
+            p->kernel = kKernelAuto;
+        } else if (!strcmp(e, "lane")) {
+            p->kernel = kKernelLane;
+        } else if (!strcmp(e, "shared")) {
+            p->kernel = kKernelShared;
+        } else {
+            fail(SHA1CHUNK_EINVAL, "pv: SHA1CHUNK_PV_KERNEL must be auto, lane or shared, not \"%.32s\"", e);
+            delete p;
+            return nullptr;
+        }
+    }
     if (const char* e = getenv("SHA1CHUNK_PV_STATS")) p->stats = atoi(e) != 0;
     p->data_bytes = p->stride * sessions;
     const size_t o_exp = 0, o_res = o_exp + 32 * sessions, o_done = o_res + 32 * sessions,
@@ -314,8 +356,13 @@ void* s1be_pv_create(size_t sessions, uint32_t max_chunk_len) {
     p->result = reinterpret_cast<uint32_t*>(p->meta + o_res);
     p->done = reinterpret_cast<uint32_t*>(p->meta + o_done);
     p->work = reinterpret_cast<PvEntry*>(p->meta + o_work);
-    bool ok = hipMalloc(reinterpret_cast<void**>(&p->state), 20 * sessions) == hipSuccess &&
+    // the midstates, then the dummy line on a 128-byte boundary (zeroed: what
+    // it holds is loaded and discarded)
+    const size_t o_dummy = round_up(20 * sessions, kAlign);
+    bool ok = hipMalloc(reinterpret_cast<void**>(&p->state), o_dummy + 64) == hipSuccess &&
+              hipMemset(reinterpret_cast<uint8_t*>(p->state) + o_dummy, 0, 64) == hipSuccess &&
               s1rt::stream_create(&p->stream) == 0;
+    if (ok) p->dummy = reinterpret_cast<const uint8_t*>(p->state) + o_dummy;
     for (PvLaunch& L : p->launch)
         ok = ok && hipEventCreateWithFlags(&L.ev, hipEventDisableTiming) == hipSuccess;
     if (!ok) {
@@ -363,10 +410,8 @@ void* s1be_pv_open(void* pv, uint32_t len, const uint8_t expected[20], uint64_t 
     return p->data + p->stride * s;
 }
 
-int s1be_pv_advance(void* pv, void* buf, uint32_t ready) {
-    Pv* p = static_cast<Pv*>(pv);
-    if (!p) return fail(SHA1CHUNK_EINVAL, "pv: null object");
-    std::lock_guard<std::mutex> lk(p->mu);
+// advance() without its pump: records the mark.  Caller holds p->mu.
+static int pv_apply(Pv* p, void* buf, uint32_t ready) {
     const long s = pv_find(p, buf);
     if (s < 0) return fail(SHA1CHUNK_EINVAL, "pv: %p is not an open session's buffer", buf);
     PvSession& S = p->ses[s];
@@ -379,8 +424,56 @@ int s1be_pv_advance(void* pv, void* buf, uint32_t ready) {
         ++p->pending;
     }
     if (S.complete || (ready & ~63u) > S.issued) pv_mark_dirty(p, static_cast<uint32_t>(s));
+    return SHA1CHUNK_OK;
+}
+
+int s1be_pv_advance(void* pv, void* buf, uint32_t ready) {
+    Pv* p = static_cast<Pv*>(pv);
+    if (!p) return fail(SHA1CHUNK_EINVAL, "pv: null object");
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (int rc = pv_apply(p, buf, ready)) return rc;
     HIP_TRY(hipSetDevice(p->dev));
     return pv_pump(p);
+}
+
+// n advances under one lock, one pump -- one launch decision -- at the end.
+// The pairs before a refused one still go to the device; its error (and
+// text) is what the call returns.
+int s1be_burst_advance(void* pv, void* const* bufs, const uint32_t* ready, size_t n, size_t* applied) {
+    Pv* p = static_cast<Pv*>(pv);
+    if (applied) *applied = 0;
+    if (!p || (n && (!bufs || !ready))) return fail(SHA1CHUNK_EINVAL, "pv: null argument");
+    std::lock_guard<std::mutex> lk(p->mu);
+    int rc = SHA1CHUNK_OK;
+    size_t i = 0;
+    for (; i < n; ++i)
+        if ((rc = pv_apply(p, bufs[i], ready[i]))) break;
+    if (applied) *applied = i;
+    if (rc) {
+        const std::string text = s1be_last_error();  // a failing pump would overwrite it
+        if (hipSetDevice(p->dev) == hipSuccess) (void)pv_pump(p);
+        return fail(rc, "%s", text.c_str());
+    }
+    HIP_TRY(hipSetDevice(p->dev));
+    return pv_pump(p);
+}
+
+int s1be_progress_stats(void* pv, void* out, size_t size) {
+    Pv* p = static_cast<Pv*>(pv);
+    if (!p || !out) return fail(SHA1CHUNK_EINVAL, "pv: null argument");
+    sha1chunk_progress_stats_t st;
+    memset(&st, 0, sizeof st);
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        st.launches = p->n_launch;
+        st.launches_shared = p->n_launch_shared;
+        st.entries = p->n_entries;
+        st.blocks = p->n_blocks;
+        st.kernel = static_cast<uint32_t>(p->kernel);
+        st.depth = static_cast<uint32_t>(p->depth);
+    }
+    memcpy(out, &st, std::min(size, sizeof st));
+    return SHA1CHUNK_OK;
 }
 
 int s1be_pv_hashed(void* pv, const void* buf, uint32_t* bytes) {
@@ -459,9 +552,11 @@ void s1be_pv_destroy(void* pv) {
     Pv* p = static_cast<Pv*>(pv);
     if (!p) return;
     if (p->stats)
-        fprintf(stderr, "{\"pv_stats\": {\"depth\": %d, \"launches\": %llu, \"entries\": %llu, \"blocks\": %llu}}\n",
-                p->depth, (unsigned long long)p->n_launch, (unsigned long long)p->n_entries,
-                (unsigned long long)p->n_blocks);
+        fprintf(stderr,
+                "{\"pv_stats\": {\"depth\": %d, \"launches\": %llu, \"launches_shared\": %llu, \"entries\": %llu, "
+                "\"blocks\": %llu}}\n",
+                p->depth, (unsigned long long)p->n_launch, (unsigned long long)p->n_launch_shared,
+                (unsigned long long)p->n_entries, (unsigned long long)p->n_blocks);
     pv_release(p);
 }
 

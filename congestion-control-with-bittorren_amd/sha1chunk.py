@@ -116,6 +116,8 @@ _SIGNATURES = [
     ("sha1chunk_pv_close", C.c_int, [_vp, _vp]),
     ("sha1chunk_pv_pending", C.c_size_t, [_vp]),
     ("sha1chunk_pv_destroy", None, [_vp]),
+    ("sha1chunk_burst_advance", C.c_int, [_vp, C.POINTER(_vp), _u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("sha1chunk_progress_stats", C.c_int, [_vp, _vp, C.c_size_t]),
     ("sha1chunk_device_count", C.c_int, []),
     ("sha1chunk_set_device", C.c_int, [C.c_int]),
     ("sha1chunk_get_device", C.c_int, []),
@@ -124,6 +126,19 @@ _SIGNATURES = [
     ("sha1chunk_last_error", C.c_char_p, []),
     ("sha1chunk_version", C.c_char_p, []),
 ]
+
+
+class ProgressStats(C.Structure):
+    """sha1chunk_progress_stats_t (include/sha1chunk.h)."""
+    _fields_ = [
+        ("launches", C.c_uint64),
+        ("launches_shared", C.c_uint64),
+        ("entries", C.c_uint64),
+        ("blocks", C.c_uint64),
+        ("kernel", C.c_uint32),
+        ("depth", C.c_uint32),
+    ]
+
 
 _lib: C.CDLL | None = None
 
@@ -440,6 +455,33 @@ class ProgressiveVerifier:
     def advance(self, r: "Reservation", ready: int) -> None:
         """Bytes [0, ready) of the session are final; ready == length completes it."""
         _check(lib().sha1chunk_pv_advance(self._p, r.ptr, ready), "sha1chunk_pv_advance")
+
+    def advance_many(self, pairs) -> int:
+        """advance() for every (reservation, ready) of `pairs`, in order, in
+        one call (sha1chunk_burst_advance): one lock, one launch decision.
+        Returns the number applied; a refused pair raises, with the pairs
+        before it applied and their count in the error's `.applied`."""
+        pairs = list(pairs)
+        n = len(pairs)
+        bufs = (_vp * max(n, 1))(*[r.ptr for r, _ in pairs])
+        marks = (C.c_uint32 * max(n, 1))(*[ready for _, ready in pairs])
+        applied = C.c_size_t(0)
+        rc = lib().sha1chunk_burst_advance(self._p, bufs, marks, n, C.byref(applied))
+        if rc < 0:
+            err = Sha1ChunkError(rc, "sha1chunk_burst_advance",
+                                 lib().sha1chunk_last_error().decode(errors="replace"))
+            err.applied = applied.value
+            raise err
+        return applied.value
+
+    def stats(self) -> dict:
+        """The object's launch counters (sha1chunk_progress_stats): launches,
+        launches_shared, entries, blocks, kernel ("auto" / "lane" /
+        "shared") and depth."""
+        st = ProgressStats()
+        _check(lib().sha1chunk_progress_stats(self._p, C.byref(st), C.sizeof(st)), "sha1chunk_progress_stats")
+        return {"launches": st.launches, "launches_shared": st.launches_shared, "entries": st.entries,
+                "blocks": st.blocks, "kernel": ("auto", "lane", "shared")[st.kernel], "depth": st.depth}
 
     def hashed(self, r: "Reservation") -> int:
         """Bytes of the session the device has confirmed hashed."""

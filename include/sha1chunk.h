@@ -336,7 +336,8 @@ void sha1chunk_vq_destroy(sha1chunk_vq *q);
  * per packet up to 32 MB/s): fed all at once its verdict comes 10.2-10.8 ms
  * after the last byte, one lane's whole chain, more than the queue's.  64 /
  * 256 sessions fed at once hash at 167-476 / 141-174 MB/s in aggregate (each
- * lane's 16-byte reads over PCIe are the bound). */
+ * lane's 16-byte reads over PCIe are the bound) on that kernel; the
+ * shared-load kernel below is for them. */
 typedef struct sha1chunk_pv sha1chunk_pv;
 sha1chunk_pv *sha1chunk_pv_create(size_t sessions, uint32_t max_chunk_len);
 void *sha1chunk_pv_open(sha1chunk_pv *p, uint32_t len, const uint8_t expected[20], uint64_t tag);
@@ -347,6 +348,59 @@ long sha1chunk_pv_poll(sha1chunk_pv *p, uint64_t *tags, uint8_t *mismatch, uint8
 int sha1chunk_pv_close(sha1chunk_pv *p, void *buf);
 size_t sha1chunk_pv_pending(const sha1chunk_pv *p);
 void sha1chunk_pv_destroy(sha1chunk_pv *p);
+
+/* Many sessions at once.  A receive loop that has just handled packets of k
+ * sessions (one select() round of the peer) states all k marks in one call:
+ * one lock and one launch decision instead of k, so the launch that follows
+ * carries every session's new blocks instead of the first caller's alone.
+ *
+ * Apply n (buffer, mark) pairs in order, each exactly as sha1chunk_pv_advance
+ * would, under one lock and with one launch decision at the end.  Stops at
+ * the first pair advance() would refuse: returns its error, *applied (may be
+ * NULL) = pairs applied before it, and the applied ones still go to the
+ * device.  n == 0 is a pump.  Never waits for the device. */
+int sha1chunk_burst_advance(sha1chunk_pv *p, void *const *bufs, const uint32_t *ready,
+                            size_t n, size_t *applied);
+
+/* Which kernel a launch takes: SHA1CHUNK_PV_KERNEL=auto|lane|shared, read by
+ * create() (anything else: create fails, SHA1CHUNK_EINVAL).  `lane` is one
+ * lane per session, each lane reading its own buffer (csrc/sha1_progress.hip);
+ * `shared` lays a wave's loads out four lanes per session, so that one load
+ * instruction reads 16 sessions' whole 64-byte blocks instead of 64 quarter
+ * blocks (csrc/sha1_progress_shared.hip); both force the choice for every
+ * launch.  `auto`, the default: a launch with a single work-list entry always
+ * takes the lane kernel -- a lone session's path is the one measured above --
+ * and a larger one the shared kernel from 64 entries that carry a whole block
+ * (the smallest session count at which it measured faster, below).
+ * The counters below say what an object's launches were.
+ *
+ * The rule counts the entries of one launch, not the object's sessions: an
+ * object with fewer than 64 sessions, or a receive round in which fewer than
+ * 64 sessions gained a whole block, stays on the lane kernel under `auto`;
+ * set SHA1CHUNK_PV_KERNEL=shared to use the shared kernel there.
+ *
+ * Measured on MI355X (tools/pv_latency_bench run C, profiles/pv_shared.jsonl,
+ * DESIGN.md section 6; median (min-max) of six runs in two sittings,
+ * aggregate MB/s, lane / shared forced): fed one burst per round 4 sessions
+ * 195 (181-210) / 208 (207-208), 16: 768 (732-878) / 829 (828-833), 64: 190
+ * (143-239) / 2208 (1815-2333), 256: 176 (167-211) / 8633 (7384-9117); fed
+ * one advance per packet 64: 217 (194-280) / 1531 (1150-1696), 256: 202
+ * (158-463) / 2492 (2401-2562).  64 is the smallest measured count at which
+ * the shared kernel's median passes the lane kernel's by more than the lane
+ * kernel's spread.  Under `auto` (three runs): 64 sessions 1396 (1347-1615)
+ * per packet / 1952 (1873-2324) per round, 256: 2274 (2203-2570) / 7460
+ * (7385-8636); 4 and 16 sessions run on the lane kernel.  A lone session's
+ * last-advance-to-verdict time is unchanged (29.2-31.0 us against the parent
+ * build's 29.4-30.3, every chunk 27.9-32.5).  Not measured: session counts
+ * between 16 and 64, several devices, a real congestion-controlled peer. */
+typedef struct {
+    uint64_t launches, launches_shared; /* kernels enqueued; of those, shared-load */
+    uint64_t entries, blocks;           /* work-list entries and 64-byte blocks issued */
+    uint32_t kernel;                    /* 0 auto, 1 lane, 2 shared */
+    uint32_t depth;
+} sha1chunk_progress_stats_t;
+/* size = sizeof the caller's struct (fields beyond it are not written). */
+int sha1chunk_progress_stats(sha1chunk_pv *p, sha1chunk_progress_stats_t *out, size_t size);
 
 /* Device management. */
 int sha1chunk_device_count(void);

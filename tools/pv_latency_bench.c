@@ -13,12 +13,15 @@
  *           the verdict then trails the last packet by the backlog.
  *   run B   the same chunk through sha1chunk_vq_submit on a lone-chunk
  *           queue: the existing path, the reference for the time.
- *   run C   64 and 256 concurrent sessions advanced round-robin one packet
- *           at a time: aggregate bytes/s; the launches issued come from the
- *           object's SHA1CHUNK_PV_STATS line on stderr.
+ *   run C   4, 16, 64 and 256 concurrent sessions advanced round-robin one
+ *           packet at a time: aggregate bytes/s, fed two ways -- "per_call",
+ *           one sha1chunk_pv_advance per session and packet, and "burst", one
+ *           sha1chunk_burst_advance per round-robin round -- with the kernel
+ *           choice and the launches issued (sha1chunk_progress_stats).
  *
  * One JSON line per run on stdout.  SHA1CHUNK_PV_DEPTH (2, 4, 8) selects the
- * kernel's prefetch depth for the A/B of DESIGN.md section 6.
+ * lane kernel's prefetch depth and SHA1CHUNK_PV_KERNEL (auto, lane, shared)
+ * the kernel, for the A/Bs of DESIGN.md section 6.
  *   usage: pv_latency_bench [chunks (default 24)]
  */
 #define _GNU_SOURCE
@@ -109,21 +112,28 @@ static double vq_chunk(sha1chunk_vq *q, const uint8_t *chunk, const uint8_t *dig
     return t1 - t0;
 }
 
-static void run_c(const uint8_t *chunk, const uint8_t *dig, const char *depth, int S) {
+static void run_c(const uint8_t *chunk, const uint8_t *dig, const char *depth, int S, int burst) {
+    static const char *const kernels[] = {"auto", "lane", "shared"};
     sha1chunk_pv *p = sha1chunk_pv_create((size_t)S, LEN);
     if (!p) die("create (run C)");
     static uint8_t *buf[MAXN];
+    static uint32_t marks[MAXN];
+    sha1chunk_progress_stats_t st0, st1;
     for (int pass = 0; pass < 2; ++pass) { /* pass 0 warms (code object, page faults) */
         for (int s = 0; s < S; ++s)
             while (!(buf[s] = (uint8_t *)sha1chunk_pv_open(p, LEN, dig, (uint64_t)s)))
                 if (!strstr(sha1chunk_last_error(), "in use")) die("open (run C)");
+        if (sha1chunk_progress_stats(p, &st0, sizeof st0)) die("stats (run C)");
         const double t0 = now_us();
         for (uint32_t mark = 0; mark < LEN;) {
             const uint32_t step = LEN - mark < PKT ? LEN - mark : PKT;
             for (int s = 0; s < S; ++s) {
                 memcpy(buf[s] + mark, chunk + mark, step);
-                if (sha1chunk_pv_advance(p, buf[s], mark + step)) die("advance (run C)");
+                marks[s] = mark + step;
+                if (!burst && sha1chunk_pv_advance(p, buf[s], mark + step)) die("advance (run C)");
             }
+            if (burst && sha1chunk_burst_advance(p, (void *const *)buf, marks, (size_t)S, NULL))
+                die("burst advance (run C)");
             mark += step;
         }
         const double t_fed = now_us();
@@ -139,11 +149,16 @@ static void run_c(const uint8_t *chunk, const uint8_t *dig, const char *depth, i
         }
         const double t1 = now_us();
         for (int s = 0; s < S; ++s) sha1chunk_pv_close(p, buf[s]);
+        if (sha1chunk_progress_stats(p, &st1, sizeof st1)) die("stats (run C)");
         if (pass == 1) {
-            printf("{\"run\": \"C\", \"depth\": %s, \"sessions\": %d, \"chunk_bytes\": %d, \"feed_ms\": %.3f, "
-                   "\"total_ms\": %.3f, \"tail_after_last_packet_ms\": %.3f, \"bytes_per_s\": %.4g}\n",
-                   depth, S, LEN, (t_fed - t0) * 1e-3, (t1 - t0) * 1e-3, (t1 - t_fed) * 1e-3,
-                   (double)S * LEN / ((t1 - t0) * 1e-6));
+            printf("{\"run\": \"C\", \"depth\": %s, \"kernel\": \"%s\", \"feed\": \"%s\", \"sessions\": %d, "
+                   "\"chunk_bytes\": %d, \"feed_ms\": %.3f, \"total_ms\": %.3f, \"tail_after_last_packet_ms\": %.3f, "
+                   "\"bytes_per_s\": %.4g, \"launches\": %llu, \"launches_shared\": %llu, \"entries\": %llu}\n",
+                   depth, kernels[st1.kernel < 3 ? st1.kernel : 0], burst ? "burst" : "per_call", S, LEN,
+                   (t_fed - t0) * 1e-3, (t1 - t0) * 1e-3, (t1 - t_fed) * 1e-3, (double)S * LEN / ((t1 - t0) * 1e-6),
+                   (unsigned long long)(st1.launches - st0.launches),
+                   (unsigned long long)(st1.launches_shared - st0.launches_shared),
+                   (unsigned long long)(st1.entries - st0.entries));
             fflush(stdout);
         }
     }
@@ -187,8 +202,9 @@ int main(int argc, char **argv) {
     stats_line("B_vq_submit_lone_chunk", depth, v, N, "");
     sha1chunk_vq_destroy(q);
 
-    run_c(chunk, dig, depth, 64);
-    run_c(chunk, dig, depth, 256);
+    static const int counts[] = {4, 16, 64, 256};
+    for (size_t i = 0; i < sizeof counts / sizeof *counts; ++i)
+        for (int burst = 0; burst < 2; ++burst) run_c(chunk, dig, depth, counts[i], burst);
     free(chunk);
     return 0;
 }
