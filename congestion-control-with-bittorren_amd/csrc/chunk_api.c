@@ -1,6 +1,6 @@
 /*
  * chunk_api.c -- the reference's C hashing API, re-implemented on top of the
- * gfx950 batch engine (sha1_runtime.hip).  Same names, signatures, return
+ * gfx950 batch engine (sha1_runtime.hip, rt_file.hip).  Same names, signatures, return
  * conventions and stdout side effects as /root/reference:
  *
  *   SHA1Init / SHA1Update / SHA1Final   sha.h:58-60, sha.c:149-558
@@ -18,7 +18,7 @@
  * SURVEY.md 7.1 step 2, 8(b)), since one message is one serial chain that a
  * GPU lane runs ~30x slower than a CPU core; make_chunks on larger files and
  * streams, and the master-file index, run on the gfx950 kernels
- * (sha1_runtime.hip), as everything does under SHA1CHUNK_HOST_SMALL=0.  A
+ * (rt_file.hip, sha1_runtime.hip), as everything does under SHA1CHUNK_HOST_SMALL=0.  A
  * device is required either way.  The reference
  * reports failures by printing and exit(-1) (chunk.c:171-178); these void
  * functions do the same when the engine fails (no device, HIP error), so a

@@ -5,7 +5,9 @@
  * section 2): the reference's hashing symbols (chunk_api.c, chunk_file.c)
  * and the sha1chunk_* batch API of include/sha1chunk.h.  It depends on libc
  * alone.  Every call that reaches the GPU is forwarded to the HIP backend,
- * libsha1chunk_hip.so (sha1_runtime.hip + the gfx950 kernels), which this
+ * libsha1chunk_hip.so (the host runtime -- rt_device.hip, sha1_runtime.hip,
+ * rt_file.hip, vq.hip, vq_persistent.hip, sha1_pv.hip -- + the gfx950 kernels;
+ * it exports its s1be_* entry points only, backend.map), which this
  * file dlopen()s from its own directory on the first such call -- so a
  * process that only makes single-message host calls (below) never loads the
  * HIP runtime: loading libamdhip64 costs ~11 ms and starting it 50-250 ms

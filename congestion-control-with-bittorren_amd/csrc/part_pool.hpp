@@ -1,8 +1,8 @@
 // part_pool.hpp -- host-side helper threads of the SHA-1 chunk runtime
-// (sha1_runtime.hip): the verify queue's chunk copies, the pageable-batch
-// packing and the file pipeline's parallel preads run their pieces on a
-// PartPool.  Plain C++ (no HIP), so tests/test_sanitizers.py can also run it
-// under ThreadSanitizer on the CPU.
+// (vq.hip, vq_persistent.hip; sha1_runtime.hip; rt_file.hip): the verify
+// queue's chunk copies, the pageable-batch packing and the file pipeline's
+// parallel preads run their pieces on a PartPool.  Plain C++ (no HIP), so
+// tests/test_sanitizers.py can also run it under ThreadSanitizer on the CPU.
 #pragma once
 
 #include <algorithm>
@@ -32,7 +32,7 @@ inline void cpu_relax() { __builtin_ia32_pause(); }
 class PartPool {
 public:
     // cpus (optional): the helpers run on these host CPUs only -- the ones
-    // near the GPU whose pinned buffers they fill (sha1_runtime.hip
+    // near the GPU whose pinned buffers they fill (rt_device.hip
     // near_cpus); the calling thread's own placement is the caller's
     explicit PartPool(int helpers, const cpu_set_t* cpus = nullptr) {
         if (cpus) {
@@ -139,7 +139,7 @@ private:
 
 // The CPUs of a sysfs cpulist ("0-63,128-191\n") that are also in `allowed`,
 // into *out; returns their count (malformed pieces are skipped).  The
-// runtime's NUMA placement (sha1_runtime.hip near_cpus) reads the GPU's
+// runtime's NUMA placement (rt_device.hip near_cpus) reads the GPU's
 // node's list with it.
 inline int cpus_from_list(const char* list, const cpu_set_t& allowed, cpu_set_t* out) {
     CPU_ZERO(out);

@@ -67,7 +67,7 @@ hipError_t launch_mixed(const BatchArgs& A, const uint32_t* sorted_len, const Bi
 hipError_t launch_plan_layout(const BatchArgs& A, const uint32_t* sorted_len, const BigFix* big, uint32_t* plan,
                               hipStream_t st);
 // Persistent verify-queue drain (sha1_kernels.hip, vq drain; host side in
-// sha1_runtime.hip, the persistent sha1chunk_vq).  The queue's rings live in
+// vq_persistent.hip, the persistent sha1chunk_vq).  The queue's rings live in
 // coherent pinned host memory, which the kernel reads over PCIe (no copy
 // engine, no launch per batch); results go back to host memory.
 struct VqDrainArgs {

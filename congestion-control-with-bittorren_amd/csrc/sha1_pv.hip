@@ -44,8 +44,9 @@
 
 namespace {
 using s1rt::fail;
+using s1rt::kAlign;  // every session buffer starts on a 128-byte line
+using s1rt::round_up;
 
-constexpr size_t kAlign = 128;  // every session buffer starts on a 128-byte line
 constexpr int kLaunchSlots = 2;
 enum { kKernelAuto = 0, kKernelLane = 1, kKernelShared = 2 };
 // `auto` takes the shared-load kernel for a work list with at least this
@@ -57,8 +58,6 @@ enum { kKernelAuto = 0, kKernelLane = 1, kKernelShared = 2 };
 // rate, 820 against 807 (736-861).  It counts one launch's entries: fewer
 // than 64 sessions with a new block stay on the lane kernel.
 constexpr uint32_t kSharedThreshold = 64;
-
-inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 struct PvSession {
     bool open = false;       // handed out by open(), not yet freed
@@ -276,7 +275,7 @@ long pv_find(const Pv* p, const void* buf) {
 // holds a few large rings by exact size, which these would push out.)
 uint8_t* pinned_alloc(size_t bytes) {
     void* p = nullptr;
-    const unsigned flags = s1rt::pinned_ring_flags();
+    const unsigned flags = s1rt::ring_flags();
     if (hipHostMalloc(&p, bytes, flags) == hipSuccess) return static_cast<uint8_t*>(p);
     (void)hipGetLastError();
     if (flags != hipHostMallocCoherent && hipHostMalloc(&p, bytes, hipHostMallocCoherent) == hipSuccess)
@@ -301,17 +300,15 @@ void pv_release(Pv* p) {
 
 extern "C" {
 
-const char* s1be_last_error(void);  // sha1_runtime.hip
-
 void* s1be_pv_create(size_t sessions, uint32_t max_chunk_len) {
     if (sessions == 0 || sessions > (1u << 20)) {
         fail(SHA1CHUNK_EINVAL, "pv: 1..2^20 sessions required");
         return nullptr;
     }
-    int hip_id = 0, cus = 0;
-    if (s1rt::acquire_device(&hip_id, &cus)) return nullptr;
+    s1rt::Device* D;
+    if (s1rt::get_device(&D)) return nullptr;
     Pv* p = new Pv();
-    p->dev = hip_id;
+    p->dev = D->id;
     p->sessions = static_cast<uint32_t>(sessions);
     p->maxlen = max_chunk_len;
     p->stride = round_up(std::max<size_t>(max_chunk_len, 1), kAlign);
@@ -361,7 +358,7 @@ void* s1be_pv_create(size_t sessions, uint32_t max_chunk_len) {
     const size_t o_dummy = round_up(20 * sessions, kAlign);
     bool ok = hipMalloc(reinterpret_cast<void**>(&p->state), o_dummy + 64) == hipSuccess &&
               hipMemset(reinterpret_cast<uint8_t*>(p->state) + o_dummy, 0, 64) == hipSuccess &&
-              s1rt::stream_create(&p->stream) == 0;
+              s1rt::vq_stream_create(&p->stream) == 0;
     if (ok) p->dummy = reinterpret_cast<const uint8_t*>(p->state) + o_dummy;
     for (PvLaunch& L : p->launch)
         ok = ok && hipEventCreateWithFlags(&L.ev, hipEventDisableTiming) == hipSuccess;

@@ -161,11 +161,16 @@ def test_front_end_links_libc_only(built):
     backend = os.path.join(PKG_DIR, "libsha1chunk_hip.so")
     assert os.path.exists(backend)
     assert "amdhip64" in subprocess.run(["ldd", backend], capture_output=True, text=True).stdout
-    syms = subprocess.run(["nm", "-D", "--defined-only", backend], capture_output=True,
-                          text=True).stdout.split()
+    nm = subprocess.run(["nm", "-D", "--defined-only", backend], capture_output=True, text=True).stdout
+    syms = nm.split()
     assert not [s for s in syms if s.startswith("sha1chunk_") or s in ("shahash", "SHA1Init")]
     assert "s1be_hash_batch" in syms
     assert "s1be_sort_order_async" in syms  # diagnostics for tests/test_gpu_sort.py
+    # every defined dynamic symbol is an entry point (csrc/backend.map): no
+    # launcher, kernel stub, class or template instantiation leaks out
+    names = [line.split()[-1] for line in nm.splitlines() if line.strip()]
+    leaked = [n for n in names if not n.startswith("s1be_")]
+    assert names and not leaked, leaked
 
 
 def test_missing_backend_fails_loudly(tmp_path, built):
