@@ -125,6 +125,12 @@ hipError_t launch_progress(const PvArgs& P, int depth, hipStream_t st);
 // lanes per entry (sha1_progress_shared.hip): for many sessions at once.
 hipError_t launch_progress_shared(const PvArgs& P, hipStream_t st);
 
+// One workgroup of kSynthThreads per chunk.  A launch holds fewer than 2^32
+// work-items per dimension (the dispatch packet's grid size is a 32-bit count
+// of work-items), so one call fills at most kSynthMaxChunks chunks; a larger
+// count is hipErrorInvalidValue (the C ABI refuses it before it gets here).
+constexpr uint32_t kSynthThreads = 256;
+constexpr uint64_t kSynthMaxChunks = 0xffffffffull / kSynthThreads;  // 2^24 - 1
 hipError_t launch_synth(uint8_t* dst, const uint64_t* off, const uint32_t* lens, uint32_t ulen,
                         uint64_t first, uint64_t count, uint64_t seed, hipStream_t st);
 hipError_t launch_compare(const uint8_t* dig, const uint8_t* exp, uint32_t n, uint8_t* mismatch,

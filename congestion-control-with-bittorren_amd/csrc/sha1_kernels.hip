@@ -1165,7 +1165,7 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
 
 // One workgroup per chunk: chunk c (global index first + blockIdx.x) of
 // length len is written at dst + off.  dst + off must be 8-byte aligned.
-__global__ __launch_bounds__(256) void synth_fill_kernel(uint8_t* dst, const uint64_t* off,
+__global__ __launch_bounds__(kSynthThreads) void synth_fill_kernel(uint8_t* dst, const uint64_t* off,
                                                          const uint32_t* lens, uint32_t ulen,
                                                          uint64_t first, uint64_t seed) {
     const uint64_t c = blockIdx.x;
@@ -1313,7 +1313,8 @@ hipError_t launch_vq_drain(const VqDrainArgs& Q, uint32_t grid, hipStream_t st) 
 hipError_t launch_synth(uint8_t* dst, const uint64_t* off, const uint32_t* lens, uint32_t ulen,
                         uint64_t first, uint64_t count, uint64_t seed, hipStream_t st) {
     if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(synth_fill_kernel, dim3((uint32_t)count), dim3(256), 0, st, dst, off, lens,
+    if (count > kSynthMaxChunks) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(synth_fill_kernel, dim3((uint32_t)count), dim3(kSynthThreads), 0, st, dst, off, lens,
                        ulen, first, seed);
     return hipGetLastError();
 }

@@ -503,7 +503,9 @@ int s1be_mixed_order_async(const uint32_t* d_lengths, const uint64_t* d_offsets,
 
 int s1be_compare_device_async(const uint8_t* d_digests, const uint8_t* d_expected, size_t n,
                                    uint8_t* d_mismatch, void* stream) {
-    if (n > 0xffffffffu) return fail(SHA1CHUNK_EINVAL, "n too large");
+    // 256 threads per workgroup, one per chunk: the launch rounds n up to whole
+    // workgroups and holds fewer than 2^32 work-items
+    if (n > 0xffffffffu - 255u) return fail(SHA1CHUNK_EINVAL, "n too large: at most 2^32 - 256 per call");
     if (n && (!d_digests || !d_expected || !d_mismatch))
         return fail(SHA1CHUNK_EINVAL, "null device pointer");
     Device* D;
@@ -623,9 +625,19 @@ int s1be_finish(const uint32_t state[5], uint64_t prefix_bytes, const void* tail
     return SHA1CHUNK_OK;
 }
 
+// One workgroup per chunk (launch_synth): a count one launch cannot express
+// (kSynthMaxChunks, sha1_kernels.h) is refused, not truncated to 32 bits.
+static int check_synth_count(uint64_t count) {
+    if (count > kSynthMaxChunks)
+        return fail(SHA1CHUNK_EINVAL, "synthetic fill of %llu chunks: at most %llu (2^24 - 1) per call",
+                    static_cast<unsigned long long>(count), static_cast<unsigned long long>(kSynthMaxChunks));
+    return SHA1CHUNK_OK;
+}
+
 int s1be_synth_fill_async(void* d_dst, uint64_t first, uint64_t count, uint32_t chunk_len,
                                uint64_t seed, void* stream) {
     if (count && !d_dst) return fail(SHA1CHUNK_EINVAL, "null pointer");
+    if (int rc = check_synth_count(count)) return rc;
     if ((reinterpret_cast<uintptr_t>(d_dst) & 7u) || (chunk_len & 7u && count > 1))
         return fail(SHA1CHUNK_EALIGN, "synthetic chunks must start 8-byte aligned");
     Device* D;
@@ -641,6 +653,7 @@ int s1be_synth_fill_ragged_async(void* d_base, const uint64_t* d_offsets,
                                       const uint32_t* d_lengths, uint64_t first, uint64_t count,
                                       uint64_t seed, void* stream) {
     if (count && (!d_base || !d_offsets || !d_lengths)) return fail(SHA1CHUNK_EINVAL, "null pointer");
+    if (int rc = check_synth_count(count)) return rc;
     Device* D;
     int rc = get_device(&D);
     if (rc) return rc;

@@ -560,6 +560,30 @@ def compare_device(digests, expected, mismatch, stream=None) -> None:
            "sha1chunk_compare_device_async")
 
 
+def _dev_ptr(t, ctype):
+    """A device tensor's address (or a plain int) as the ctypes pointer type
+    a host/device entry point is declared with."""
+    return C.cast(C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t)), ctype)
+
+
+def hash_batch_device(base, offsets, lengths, digests, n: int | None = None) -> None:
+    """sha1chunk_hash_batch(..., SHA1CHUNK_DEVICE): every buffer a tensor on
+    the current device (or a raw address).  Synchronous: the digests are in
+    `digests` when the call returns."""
+    n = offsets.numel() if n is None else n
+    _check(lib().sha1chunk_hash_batch(_dev_ptr(base, _vp), _dev_ptr(offsets, _u64p), _dev_ptr(lengths, _u32p), n,
+                                      _dev_ptr(digests, _u8p), DEVICE), "sha1chunk_hash_batch")
+
+
+def verify_batch_device(base, offsets, lengths, expected, mismatch, n: int | None = None) -> None:
+    """sha1chunk_verify_batch(..., SHA1CHUNK_DEVICE): `expected` (n x 20) and
+    `mismatch` (n bytes) are device buffers too.  Synchronous."""
+    n = offsets.numel() if n is None else n
+    _check(lib().sha1chunk_verify_batch(_dev_ptr(base, _vp), _dev_ptr(offsets, _u64p), _dev_ptr(lengths, _u32p), n,
+                                        _dev_ptr(expected, _u8p), _dev_ptr(mismatch, _u8p), DEVICE),
+           "sha1chunk_verify_batch")
+
+
 def synth_fill_device(dst, first: int, count: int, chunk_len: int = CHUNK_LEN, seed: int = SEED,
                       stream=None) -> None:
     _check(lib().sha1chunk_synth_fill_async(dst.data_ptr(), first, count, chunk_len, seed,

@@ -110,7 +110,8 @@ int sha1chunk_hash_device_async(const void *d_base, const uint64_t *d_offsets,
 int sha1chunk_hash_uniform_async(const void *d_base, uint32_t chunk_len, size_t n,
                                  uint8_t *d_digests, void *stream, int kernel);
 
-/* Device compare of computed vs expected digests -> mismatch bytes. */
+/* Device compare of computed vs expected digests -> mismatch bytes
+ * (n at most 2^32 - 256 per call). */
 int sha1chunk_compare_device_async(const uint8_t *d_digests, const uint8_t *d_expected,
                                    size_t n, uint8_t *d_mismatch, void *stream);
 
@@ -149,7 +150,12 @@ int sha1chunk_finish(const uint32_t state[5], uint64_t prefix_bytes, const void 
 
 /* Synthetic corpus generated on the device: chunk c, 64-bit
  * LE word w = splitmix64(seed ^ (c << 24) ^ w), chunks first..first+count-1
- * written back to back, chunk_len bytes each. */
+ * written back to back, chunk_len bytes each (a multiple of 8 when count > 1,
+ * else SHA1CHUNK_EALIGN).  One call fills at most 2^24 - 1 chunks (one
+ * 256-thread workgroup per chunk, fewer than 2^32 work-items per launch): a
+ * larger count is refused with SHA1CHUNK_EINVAL before anything is launched,
+ * here and in the ragged variant; fill a larger corpus in several calls,
+ * advancing `first` and the destination. */
 int sha1chunk_synth_fill_async(void *d_dst, uint64_t first, uint64_t count, uint32_t chunk_len,
                                uint64_t seed, void *stream);
 /* Ragged variant: chunk first+i of d_lengths[i] bytes at d_base + d_offsets[i]
