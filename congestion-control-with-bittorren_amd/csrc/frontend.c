@@ -6,7 +6,7 @@
  * and the sha1chunk_* batch API of include/sha1chunk.h.  It depends on libc
  * alone.  Every call that reaches the GPU is forwarded to the HIP backend,
  * libsha1chunk_hip.so (the host runtime -- rt_device.hip, sha1_runtime.hip,
- * rt_file.hip, vq.hip, vq_persistent.hip, sha1_pv.hip -- + the gfx950 kernels;
+ * rt_file.hip, vq.hip, vq_persistent.hip, sha1_pv.hip, rt_update.hip -- + the gfx950 kernels;
  * it exports its s1be_* entry points only, backend.map), which this
  * file dlopen()s from its own directory on the first such call -- so a
  * process that only makes single-message host calls (below) never loads the
@@ -97,6 +97,13 @@ static int fail(int code, const char *fmt, ...) {
     X(void, pv_destroy, (void *))                                                                 \
     X(int, burst_advance, (void *, void *const *, const uint32_t *, size_t, size_t *))            \
     X(int, progress_stats, (void *, void *, size_t))                                              \
+    X(int, init_device_async, (void *, size_t, const uint32_t *, size_t, void *))                 \
+    X(int, update_device_async, (void *, size_t, const uint32_t *, const void *, const uint64_t *, \
+                                 const uint32_t *, size_t, void *))                               \
+    X(int, final_device_async, (void *, size_t, const uint32_t *, size_t, uint8_t *, void *))     \
+    X(int, update_batch, (void *, size_t, const uint32_t *, const void *, const uint64_t *,       \
+                          const uint32_t *, size_t, unsigned))                                    \
+    X(int, final_batch, (void *, size_t, const uint32_t *, size_t, uint8_t *, unsigned))          \
     X(int, device_count, (void))                                                                  \
     X(int, set_device, (int))                                                                     \
     X(int, device_pci_bus_id, (int, char *, size_t))                                              \
@@ -832,4 +839,91 @@ FE_API int sha1chunk_burst_advance(sha1chunk_pv *p, void *const *bufs, const uin
 FE_API int sha1chunk_progress_stats(sha1chunk_pv *p, sha1chunk_progress_stats_t *out, size_t size) {
     if (!p || !out) return fail(SHA1CHUNK_EINVAL, "pv: null argument");
     FORWARD(int, progress_stats(p, out, size));
+}
+
+/* ------------------------------------- batched SHA1Init / Update / Final -- */
+/* Batch entry points: always on the gfx950 kernels (SHA1CHUNK_HOST_SMALL does
+ * not apply, as for sha1chunk_pv).  The argument checks are made here, before
+ * anything is forwarded (include/sha1chunk.h, "Argument checks"). */
+#define BATCH_MAX (0xffffffffu - 1024u) /* check_batch's limit (sha1_runtime.hip) */
+
+static int u32_cmp(const void *a, const void *b) {
+    const uint32_t x = *(const uint32_t *)a, y = *(const uint32_t *)b;
+    return x < y ? -1 : x > y;
+}
+
+/* Host forms: every entry's context inside the array and listed once. */
+static int check_context_list(size_t n_contexts, const uint32_t *index, size_t n) {
+    if (!index) {
+        if (n > n_contexts) return fail(SHA1CHUNK_EINVAL, "%zu entries over %zu contexts", n, n_contexts);
+        return SHA1CHUNK_OK;
+    }
+    uint32_t *sorted = (uint32_t *)malloc(n * sizeof *sorted);
+    if (!sorted) return fail(SHA1CHUNK_ENOMEM, "context list of %zu entries", n);
+    memcpy(sorted, index, n * sizeof *sorted);
+    qsort(sorted, n, sizeof *sorted, u32_cmp);
+    int rc = SHA1CHUNK_OK;
+    if (sorted[n - 1] >= n_contexts)
+        rc = fail(SHA1CHUNK_EINVAL, "context index %u outside the %zu contexts", sorted[n - 1], n_contexts);
+    for (size_t i = 1; !rc && i < n; ++i)
+        if (sorted[i] == sorted[i - 1]) rc = fail(SHA1CHUNK_EINVAL, "context %u listed more than once", sorted[i]);
+    free(sorted);
+    return rc;
+}
+
+/* Flags of the synchronous forms: SHA1CHUNK_HOST or SHA1CHUNK_DEVICE. */
+static int check_batch_flags(unsigned flags) {
+    if (flags & SHA1CHUNK_ALL_DEVICES) return fail(SHA1CHUNK_EINVAL, "SHA1CHUNK_ALL_DEVICES: one device per call");
+    if (flags & ~SHA1CHUNK_DEVICE) return fail(SHA1CHUNK_EINVAL, "unknown flags %#x", flags);
+    return SHA1CHUNK_OK;
+}
+
+FE_API int sha1chunk_init_device_async(void *d_contexts, size_t n_contexts, const uint32_t *d_index, size_t n,
+                                       void *stream) {
+    if (n == 0) return SHA1CHUNK_OK;
+    if (!d_contexts) return fail(SHA1CHUNK_EINVAL, "null device pointer");
+    if (n > BATCH_MAX) return fail(SHA1CHUNK_EINVAL, "n too large");
+    FORWARD(int, init_device_async(d_contexts, n_contexts, d_index, n, stream));
+}
+
+FE_API int sha1chunk_update_device_async(void *d_contexts, size_t n_contexts, const uint32_t *d_index,
+                                         const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lengths,
+                                         size_t n, void *stream) {
+    if (n == 0) return SHA1CHUNK_OK;
+    if (!d_contexts || !d_base || !d_offsets || !d_lengths) return fail(SHA1CHUNK_EINVAL, "null device pointer");
+    if (n > BATCH_MAX) return fail(SHA1CHUNK_EINVAL, "n too large");
+    FORWARD(int, update_device_async(d_contexts, n_contexts, d_index, d_base, d_offsets, d_lengths, n, stream));
+}
+
+FE_API int sha1chunk_final_device_async(void *d_contexts, size_t n_contexts, const uint32_t *d_index, size_t n,
+                                        uint8_t *d_digests, void *stream) {
+    if (n == 0) return SHA1CHUNK_OK;
+    if (!d_contexts) return fail(SHA1CHUNK_EINVAL, "null device pointer");
+    if (n > BATCH_MAX) return fail(SHA1CHUNK_EINVAL, "n too large");
+    if ((uintptr_t)d_digests & 3u) return fail(SHA1CHUNK_EALIGN, "digest buffer must be 4-byte aligned");
+    FORWARD(int, final_device_async(d_contexts, n_contexts, d_index, n, d_digests, stream));
+}
+
+FE_API int sha1chunk_update_batch(void *contexts, size_t n_contexts, const uint32_t *index, const void *base,
+                                  const uint64_t *offsets, const uint32_t *lengths, size_t n, unsigned flags) {
+    if (n == 0) return SHA1CHUNK_OK;
+    if (!contexts || !base || !offsets || !lengths) return fail(SHA1CHUNK_EINVAL, "null pointer");
+    if (n > BATCH_MAX) return fail(SHA1CHUNK_EINVAL, "n too large");
+    int rc = check_batch_flags(flags);
+    if (rc) return rc;
+    if (!(flags & SHA1CHUNK_DEVICE) && (rc = check_context_list(n_contexts, index, n))) return rc;
+    FORWARD(int, update_batch(contexts, n_contexts, index, base, offsets, lengths, n, flags));
+}
+
+FE_API int sha1chunk_final_batch(void *contexts, size_t n_contexts, const uint32_t *index, size_t n,
+                                 uint8_t *digests, unsigned flags) {
+    if (n == 0) return SHA1CHUNK_OK;
+    if (!contexts) return fail(SHA1CHUNK_EINVAL, "null pointer");
+    if (n > BATCH_MAX) return fail(SHA1CHUNK_EINVAL, "n too large");
+    int rc = check_batch_flags(flags);
+    if (rc) return rc;
+    if ((flags & SHA1CHUNK_DEVICE) && ((uintptr_t)digests & 3u))
+        return fail(SHA1CHUNK_EALIGN, "digest buffer must be 4-byte aligned");
+    if (!(flags & SHA1CHUNK_DEVICE) && (rc = check_context_list(n_contexts, index, n))) return rc;
+    FORWARD(int, final_batch(contexts, n_contexts, index, n, digests, flags));
 }

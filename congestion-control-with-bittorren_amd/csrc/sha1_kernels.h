@@ -125,6 +125,33 @@ hipError_t launch_progress(const PvArgs& P, int depth, hipStream_t st);
 // lanes per entry (sha1_progress_shared.hip): for many sessions at once.
 hipError_t launch_progress_shared(const PvArgs& P, hipStream_t st);
 
+// Batched SHA1Init / SHA1Update / SHA1Final over an array of 96-byte
+// SHA1Context structs in device memory (sha1_update.hip; host side in
+// rt_update.hip).  Entry i works on context index ? index[i] : i; an entry
+// whose context index is >= n_contexts, or whose context says more than 63
+// staged bytes, is skipped by every kernel.
+struct UpdateArgs {
+    uint8_t* ctx;           // n_contexts structs of 96 bytes, 8-byte aligned
+    uint64_t n_contexts;
+    const uint32_t* index;  // n context indices, or null: entry i is context i
+    uint32_t n;
+    // update only: entry i's piece is base[off[i] .. off[i] + len[i])
+    const uint8_t* base;
+    const uint64_t* off;
+    const uint32_t* len;
+    // update scratch, n entries each: the piece's whole-block span after the
+    // head (what the bulk launch hashes) and the packed chaining values
+    // (BatchArgs::init_state / out_state of that launch, in place)
+    uint64_t* mid_off;
+    uint32_t* mid_len;
+    uint32_t* state;
+    uint8_t* dig;  // final only: n x 20 digest bytes, 4-byte aligned, or null
+};
+hipError_t launch_update_init(const UpdateArgs& U, hipStream_t st);
+hipError_t launch_update_pre(const UpdateArgs& U, hipStream_t st);
+hipError_t launch_update_post(const UpdateArgs& U, hipStream_t st);
+hipError_t launch_update_final(const UpdateArgs& U, hipStream_t st);
+
 // One workgroup of kSynthThreads per chunk.  A launch holds fewer than 2^32
 // work-items per dimension (the dispatch packet's grid size is a 32-bit count
 // of work-items), so one call fills at most kSynthMaxChunks chunks; a larger

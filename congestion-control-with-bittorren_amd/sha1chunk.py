@@ -118,6 +118,11 @@ _SIGNATURES = [
     ("sha1chunk_pv_destroy", None, [_vp]),
     ("sha1chunk_burst_advance", C.c_int, [_vp, C.POINTER(_vp), _u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("sha1chunk_progress_stats", C.c_int, [_vp, _vp, C.c_size_t]),
+    ("sha1chunk_init_device_async", C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    ("sha1chunk_update_device_async", C.c_int, [_vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    ("sha1chunk_final_device_async", C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
+    ("sha1chunk_update_batch", C.c_int, [_vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, C.c_uint]),
+    ("sha1chunk_final_batch", C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint]),
     ("sha1chunk_device_count", C.c_int, []),
     ("sha1chunk_set_device", C.c_int, [C.c_int]),
     ("sha1chunk_get_device", C.c_int, []),
@@ -582,6 +587,98 @@ def verify_batch_device(base, offsets, lengths, expected, mismatch, n: int | Non
     _check(lib().sha1chunk_verify_batch(_dev_ptr(base, _vp), _dev_ptr(offsets, _u64p), _dev_ptr(lengths, _u32p), n,
                                         _dev_ptr(expected, _u8p), _dev_ptr(mismatch, _u8p), DEVICE),
            "sha1chunk_verify_batch")
+
+
+# ---- batched SHA1Init / SHA1Update / SHA1Final over arrays of SHA1Context ----
+CONTEXT_BYTES = 96
+CONTEXT_DTYPE = np.dtype([("totalLength", "<u8"), ("hash", "<u4", (5,)), ("bufferLength", "<u4"),
+                          ("buffer", "u1", (64,))])
+
+
+def _addr(x) -> int | None:
+    """Address of a torch tensor, a numpy array or a plain int (None stays None)."""
+    if x is None:
+        return None
+    if hasattr(x, "data_ptr"):
+        return x.data_ptr()
+    if isinstance(x, np.ndarray):
+        return x.ctypes.data
+    return int(x)
+
+
+def _count(contexts, n_contexts: int | None) -> int:
+    if n_contexts is not None:
+        return n_contexts
+    nbytes = contexts.numel() * contexts.element_size() if hasattr(contexts, "numel") else contexts.nbytes
+    return nbytes // CONTEXT_BYTES
+
+
+def init_contexts_device(contexts, index=None, n: int | None = None, n_contexts: int | None = None,
+                         stream=None) -> None:
+    """Enqueue SHA1Init of the listed contexts (a device buffer of 96-byte
+    structs; index: device uint32/int32 tensor or None for contexts 0..n-1)."""
+    nc = _count(contexts, n_contexts)
+    n = (index.numel() if index is not None else nc) if n is None else n
+    _check(lib().sha1chunk_init_device_async(_addr(contexts), nc, _addr(index), n, _stream_ptr(stream)),
+           "sha1chunk_init_device_async")
+
+
+def update_contexts_device(contexts, base, offsets, lengths, index=None, n: int | None = None,
+                           n_contexts: int | None = None, stream=None) -> None:
+    """Enqueue SHA1Update(&contexts[index[i]], base + offsets[i], lengths[i])
+    for every entry (torch CUDA tensors: offsets int64, lengths int32)."""
+    nc = _count(contexts, n_contexts)
+    n = offsets.numel() if n is None else n
+    _check(lib().sha1chunk_update_device_async(_addr(contexts), nc, _addr(index), _addr(base), _addr(offsets),
+                                               _addr(lengths), n, _stream_ptr(stream)),
+           "sha1chunk_update_device_async")
+
+
+def final_contexts_device(contexts, digests=None, index=None, n: int | None = None, n_contexts: int | None = None,
+                          stream=None) -> None:
+    """Enqueue SHA1Final of the listed contexts; digests (n, 20) uint8 on the
+    device, or None."""
+    nc = _count(contexts, n_contexts)
+    n = (index.numel() if index is not None else nc) if n is None else n
+    _check(lib().sha1chunk_final_device_async(_addr(contexts), nc, _addr(index), n, _addr(digests),
+                                              _stream_ptr(stream)), "sha1chunk_final_device_async")
+
+
+def new_contexts(n: int) -> np.ndarray:
+    """n host contexts as SHA1Init leaves them (a CONTEXT_DTYPE array)."""
+    ctx = np.zeros(n, CONTEXT_DTYPE)
+    ctx["hash"] = np.array([0x67452301, 0xEFCDAB89, 0x98BADCFE, 0x10325476, 0xC3D2E1F0], np.uint32)
+    return ctx
+
+
+def update_batch(contexts: np.ndarray, base, offsets, lengths, index=None) -> None:
+    """sha1chunk_update_batch(..., SHA1CHUNK_HOST): contexts is a writable
+    host array of 96-byte structs (CONTEXT_DTYPE), updated in place."""
+    b = np.frombuffer(base, np.uint8) if isinstance(base, (bytes, bytearray)) else \
+        np.ascontiguousarray(base).view(np.uint8).reshape(-1)
+    if b.size == 0:
+        b = np.zeros(1, np.uint8)
+    off = np.ascontiguousarray(offsets, np.uint64)
+    ln = np.ascontiguousarray(lengths, np.uint32)
+    if off.shape != ln.shape:
+        raise ValueError("offsets and lengths differ in length")
+    idx = None if index is None else np.ascontiguousarray(index, np.uint32)
+    if idx is not None and idx.shape != ln.shape:
+        raise ValueError("index and lengths differ in length")
+    _check(lib().sha1chunk_update_batch(contexts.ctypes.data, _count(contexts, None), _addr(idx), b.ctypes.data,
+                                        off.ctypes.data, ln.ctypes.data, off.size, HOST), "sha1chunk_update_batch")
+
+
+def final_batch(contexts: np.ndarray, index=None) -> np.ndarray:
+    """sha1chunk_final_batch(..., SHA1CHUNK_HOST) -> (n, 20) uint8 digests;
+    the contexts are left as SHA1Final leaves them."""
+    idx = None if index is None else np.ascontiguousarray(index, np.uint32)
+    nc = _count(contexts, None)
+    n = nc if idx is None else idx.size
+    out = np.zeros((n, DIGEST_LEN), np.uint8)
+    _check(lib().sha1chunk_final_batch(contexts.ctypes.data, nc, _addr(idx), n, out.ctypes.data, HOST),
+           "sha1chunk_final_batch")
+    return out
 
 
 def synth_fill_device(dst, first: int, count: int, chunk_len: int = CHUNK_LEN, seed: int = SEED,

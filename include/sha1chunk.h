@@ -408,6 +408,87 @@ typedef struct {
 /* size = sizeof the caller's struct (fields beyond it are not written). */
 int sha1chunk_progress_stats(sha1chunk_pv *p, sha1chunk_progress_stats_t *out, size_t size);
 
+/* ---- Batched SHA1Init / SHA1Update / SHA1Final: many messages in pieces ---
+ * The streaming trio of sha.h for N messages at once: each message has its
+ * own context, its pieces lie anywhere in host or device memory, have any
+ * length and arrive over any number of calls.  (sha1chunk_pv is the special
+ * case of receive sessions in the library's own pinned buffers, fed as a
+ * growing prefix, verify only; use it for that.)
+ *
+ * A context is the reference's SHA1Context (sha.h), passed as void * since
+ * this header does not include sha.h: SHA1CHUNK_CONTEXT_BYTES (96) bytes,
+ * totalLength (bits) at byte 0, hash[5] at byte 8, bufferLength at byte 28,
+ * buffer at byte 32.  `contexts` is an array of n_contexts such structs,
+ * 8-byte aligned.  Entry i (0 <= i < n) works on context index ? index[i] : i.
+ *
+ * Update.  After update, context c of entry i holds what SHA1Update(&ctx[c],
+ *   base + offsets[i], lengths[i]) leaves: totalLength, hash, bufferLength
+ *   and the first bufferLength bytes of buffer.  The buffer bytes at and
+ *   above bufferLength are unspecified (stale bytes in the reference too).
+ *   Nothing outside the 96 bytes is written.
+ * Final.  After final, digests[20*i ..] holds what SHA1Final returns (digests
+ *   may be NULL), and the context is left as SHA1Final leaves it: hash = the
+ *   digest words, bufferLength = 0, totalLength = the padded bit count.
+ * Init is SHA1Init.
+ * Migration.  The bytes are the struct: a context moves between these calls
+ *   and the library's SHA1Init / SHA1Update / SHA1Final by plain copy.
+ * Duplicates.  A context may appear at most once per call.  The host forms
+ *   check this: a duplicate, or an index[i] >= n_contexts, is refused with
+ *   SHA1CHUNK_EINVAL and nothing is touched.  The device forms cannot see the
+ *   list: an entry whose index is >= n_contexts is skipped by the kernels (no
+ *   read or write through it, its digest left untouched), and so is an entry
+ *   whose context has bufferLength > 63 (the reference would overrun its
+ *   buffer; this library does not index with it).  Duplicates in a device
+ *   call are UNDEFINED: the entries race on the context.
+ * Ordering.  Calls that touch the same context must be ordered by the
+ *   caller: the same stream, or the caller's own events.  The async forms
+ *   never wait for the device.
+ * Overlap.  Pieces must not overlap the contexts.
+ * Argument checks (made before anything reaches the device): n == 0 is a
+ *   successful no-op; null pointers with n > 0 and n above 2^32 - 1025 are
+ *   SHA1CHUNK_EINVAL; a device digest buffer that is not 4-byte aligned is
+ *   SHA1CHUNK_EALIGN; SHA1CHUNK_ALL_DEVICES is SHA1CHUNK_EINVAL.
+ * Routing.  Batch entry points: always on the gfx950 kernels
+ *   (csrc/sha1_update.hip and, for the whole blocks, the lane / fused / split
+ *   kernels resumed from each context's chaining value; SHA1CHUNK_FORCE_KERNEL
+ *   applies).  SHA1CHUNK_HOST_SMALL does not apply, as for sha1chunk_pv;
+ *   without a device they return SHA1CHUNK_ENODEV.
+ *
+ * The host form of update stages contexts and pieces through one pinned
+ * buffer of SHA1CHUNK_UPDATE_FILL_MIB (default 256) MiB of pieces per fill;
+ * larger batches go in several fills, a larger piece is cut at multiples of
+ * 64 bytes inside the library.  Copy and hashing do not overlap.
+ *
+ * Measured on MI355X (tools/update_batch_bench.py, profiles/update_batch.jsonl,
+ * DESIGN.md section 6; device-resident, HIP events, median (min-max) of seven
+ * repetitions in one run): 4096 contexts each fed a whole 512 KiB in one
+ * update and then finalised take 6.083 (6.078-6.110) ms against 6.048
+ * (6.043-6.109) for sha1chunk_hash_uniform_async on the same bytes; an update
+ * with nothing to hash costs 0.056 ms and final 0.014 ms.  One update call of
+ * 1484-byte pieces, calls enqueued back to back: 64 contexts 34.4 us per call
+ * (2.76 GB/s in aggregate), 256: 57.7 us (6.58 GB/s), 4096: 64.7 us
+ * (94.0 GB/s).  A lone context still hashes at one lane's rate.  Not
+ * measured: the host forms, several devices. */
+#define SHA1CHUNK_CONTEXT_BYTES 96
+
+/* Device-resident, asynchronous on `stream`; all pointers are device pointers. */
+int sha1chunk_init_device_async(void *d_contexts, size_t n_contexts, const uint32_t *d_index,
+                                size_t n, void *stream);
+int sha1chunk_update_device_async(void *d_contexts, size_t n_contexts, const uint32_t *d_index,
+                                  const void *d_base, const uint64_t *d_offsets,
+                                  const uint32_t *d_lengths, size_t n, void *stream);
+/* d_digests: n x 20 bytes, 4-byte aligned, may be NULL. */
+int sha1chunk_final_device_async(void *d_contexts, size_t n_contexts, const uint32_t *d_index,
+                                 size_t n, uint8_t *d_digests, void *stream);
+
+/* Synchronous; flags = SHA1CHUNK_HOST (everything in host memory) or
+ * SHA1CHUNK_DEVICE (everything in device memory: the async form + a wait). */
+int sha1chunk_update_batch(void *contexts, size_t n_contexts, const uint32_t *index,
+                           const void *base, const uint64_t *offsets, const uint32_t *lengths,
+                           size_t n, unsigned flags);
+int sha1chunk_final_batch(void *contexts, size_t n_contexts, const uint32_t *index, size_t n,
+                          uint8_t *digests, unsigned flags);
+
 /* Device management. */
 int sha1chunk_device_count(void);
 int sha1chunk_set_device(int device);

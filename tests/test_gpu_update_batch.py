@@ -1,0 +1,659 @@
+"""GPU: batched SHA1Init / SHA1Update / SHA1Final over arrays of SHA1Context
+(include/sha1chunk.h; csrc/sha1_update.hip, rt_update.hip).  Bit-exact against
+the oracle's streaming trio on the same 96-byte structs (and, where it was
+built, the reference's own SHA1Update / SHA1Final), and against hashlib."""
+import ctypes as C
+import hashlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import default_env
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GUARD = 0xA5
+PIECE_GUARD = 0xC3
+IV = [0x67452301, 0xEFCDAB89, 0x98BADCFE, 0x10325476, 0xC3D2E1F0]
+# what the bulk launch runs on: AUTO's own choice, and every forced kernel and split shape
+KERNEL_ENVS = {
+    "auto": {},
+    "lane": {"SHA1CHUNK_FORCE_KERNEL": "lane"},
+    "fused": {"SHA1CHUNK_FORCE_KERNEL": "fused"},
+    "split": {"SHA1CHUNK_FORCE_KERNEL": "split"},
+    "unit1": {"SHA1CHUNK_SPLIT_UNIT": "1"},
+    "unit4": {"SHA1CHUNK_SPLIT_UNIT": "4"},
+    "unit11": {"SHA1CHUNK_SPLIT_UNIT": "11"},
+}
+
+
+@pytest.fixture(scope="module")
+def dev(pkg):
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a device"
+    assert pkg.device_count() >= 1, pkg.lib().sha1chunk_last_error()
+    torch.cuda.set_device(0)
+    pkg.set_device(0)
+    return torch
+
+
+class Trio:
+    """A streaming trio over 96-byte structs held in a numpy array."""
+
+    def __init__(self, lib, prefix, dtype):
+        self.init = getattr(lib, prefix[0])
+        self.update = getattr(lib, prefix[1])
+        self.final = getattr(lib, prefix[2])
+        self.init.argtypes = [C.c_void_p]
+        self.update.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        self.final.argtypes = [C.c_void_p, C.c_void_p]
+        self.init.restype = self.update.restype = self.final.restype = None
+        self.dtype = dtype
+
+    def fresh(self, n):
+        ctx = np.zeros(n, self.dtype)
+        for i in range(n):
+            self.init(ctx.ctypes.data + 96 * i)
+        return ctx
+
+    def feed(self, ctx, i, data):
+        data = np.ascontiguousarray(data, np.uint8)
+        self.update(ctx.ctypes.data + 96 * int(i), data.ctypes.data if data.size else None, int(data.size))
+
+    def finish(self, ctx):
+        dig = np.zeros((ctx.size, 20), np.uint8)
+        for i in range(ctx.size):
+            self.final(ctx.ctypes.data + 96 * i, dig.ctypes.data + 20 * i)
+        return dig
+
+
+@pytest.fixture(scope="module")
+def trio(pkg, oracle):
+    return Trio(oracle.lib(), ("oracle_sha1_init", "oracle_sha1_update", "oracle_sha1_final"),
+                pkg.sha1chunk.CONTEXT_DTYPE)
+
+
+@pytest.fixture(scope="module")
+def ref_trio(pkg, oracle):
+    """The reference's own trio, where oracle/_ref was built."""
+    path = os.path.join(ROOT, "oracle", "_ref", "libsharef.so")
+    if not os.path.exists(path):
+        return None
+    return Trio(C.CDLL(path), ("SHA1Init", "SHA1Update", "SHA1Final"), pkg.sha1chunk.CONTEXT_DTYPE)
+
+
+def same_contexts(got, want, what):
+    """Every specified field: totalLength, hash, bufferLength and the first
+    bufferLength bytes of buffer."""
+    for f in ("totalLength", "hash", "bufferLength"):
+        bad = np.flatnonzero((got[f] != want[f]).reshape(got.size, -1).any(axis=1))
+        assert bad.size == 0, f"{what}: {f} differs at entries {bad[:8].tolist()} " \
+                              f"(got {got[f][bad[:2]].tolist()}, want {want[f][bad[:2]].tolist()})"
+    staged = np.arange(64)[None, :] < want["bufferLength"][:, None]
+    bad = np.flatnonzero(((got["buffer"] != want["buffer"]) & staged).any(axis=1))
+    assert bad.size == 0, f"{what}: staged bytes differ at entries {bad[:8].tolist()}"
+
+
+def lay_out(pieces, starts):
+    """The pieces in one buffer, piece i starting at an address = starts[i]
+    mod 16, each followed by a guard byte."""
+    off = np.zeros(len(pieces), np.uint64)
+    at = 0
+    for i, (p, s) in enumerate(zip(pieces, starts)):
+        at += (s - at) % 16
+        off[i] = at
+        at += len(p) + 1
+    data = np.full(at + 16, PIECE_GUARD, np.uint8)
+    for p, o in zip(pieces, off):
+        data[int(o):int(o) + len(p)] = p
+    return data, off, np.array([len(p) for p in pieces], np.uint32)
+
+
+class DeviceArray:
+    """The contexts on the device as slots of a larger array: a guard struct
+    before and after the array, and the listed contexts at shuffled slots
+    between unlisted ones, all guards filled with 0xA5."""
+
+    def __init__(self, torch, ctx, rng, spread=2):
+        n = ctx.size
+        self.n, self.slots = n, spread * n + 1
+        self.index = rng.permutation(self.slots)[:n].astype(np.uint32)
+        self.host = np.full((self.slots + 2) * 96, GUARD, np.uint8)
+        view = self.host[96:-96].view(ctx.dtype)
+        view[self.index] = ctx
+        self.before = self.host.copy()
+        # torch's allocations are 256-byte aligned: the array at + 96 is 8-byte aligned
+        self.dev = torch.from_numpy(self.host).cuda()
+        self.array = self.dev[96:-96]
+        self.d_index = torch.from_numpy(self.index.view(np.int32)).cuda()
+        self.dtype = ctx.dtype
+
+    def read(self):
+        """The listed contexts; checks that nothing else changed."""
+        now = self.dev.cpu().numpy()
+        listed = np.zeros(self.slots + 2, bool)
+        listed[1 + self.index.astype(np.int64)] = True
+        other = np.repeat(~listed, 96)
+        assert np.array_equal(now[other], self.before[other]), "an unlisted context or a guard changed"
+        return now[96:-96].view(self.dtype)[self.index].copy()
+
+
+def device_update(pkg, torch, arr, data, off, ln, index=None, n=None):
+    d_data = torch.from_numpy(data).cuda()
+    d_off = torch.from_numpy(off.view(np.int64)).cuda()
+    d_len = torch.from_numpy(ln.view(np.int32)).cuda()
+    pkg.sha1chunk.update_contexts_device(arr.array, d_data, d_off, d_len, index=arr.d_index if index is None else index,
+                                         n=n, n_contexts=arr.slots)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_data.cpu().numpy(), data), "the pieces changed"
+
+
+# ---- 1. the smallest shapes first, then the seam grid -----------------------
+@pytest.mark.parametrize("kernel", list(KERNEL_ENVS))
+@pytest.mark.parametrize("n", [2, 65])
+def test_smallest_shapes(pkg, dev, trio, monkeypatch, n, kernel):
+    """Update mode with more than one message per launch: n = 2 and n = 65
+    entries of 200 bytes on fresh contexts."""
+    for k, v in KERNEL_ENVS[kernel].items():
+        monkeypatch.setenv(k, v)
+    rng = np.random.default_rng(200 + n)
+    pieces = [rng.integers(0, 256, 200, dtype=np.uint8) for _ in range(n)]
+    data, off, ln = lay_out(pieces, [3 * i % 16 for i in range(n)])
+    ctx = trio.fresh(n)
+    arr = DeviceArray(dev, ctx, rng)
+    device_update(pkg, dev, arr, data, off, ln)
+    want = ctx.copy()
+    for i in range(n):
+        trio.feed(want, i, pieces[i])
+    same_contexts(arr.read(), want, f"n = {n}, {kernel}")
+
+
+B_GRID = [0, 1, 3, 4, 5, 31, 55, 56, 60, 63]
+START_GRID = [0, 1, 2, 3, 5, 8, 15]
+
+
+def _l_grid(b):
+    return [0, 1, 2, 3, 4, 5, 63 - b, 64 - b, 65 - b, 64, 65, 127, 128, 129, 128 - b, 191 - b, 192 - b, 200]
+
+
+@pytest.fixture(scope="module")
+def seam_grid(trio, ref_trio):
+    """Every (b, L, start) combination: the contexts brought to b staged bytes
+    by the oracle (every other one with 64 + b earlier bytes, so its hash is
+    not the IV), the pieces, and the oracle's contexts after the update."""
+    rng = np.random.default_rng(1260)
+    combos = [(b, L, s) for b in B_GRID for L in _l_grid(b) for s in START_GRID]
+    assert len(combos) == 1260
+    ctx = trio.fresh(len(combos))
+    pieces = []
+    for i, (b, L, s) in enumerate(combos):
+        trio.feed(ctx, i, rng.integers(0, 256, b + (64 if i % 2 else 0), dtype=np.uint8))
+        pieces.append(rng.integers(0, 256, L, dtype=np.uint8))
+    assert (ctx["bufferLength"] == [c[0] for c in combos]).all()
+    assert (ctx["hash"][1::2] != np.array(IV, np.uint32)).any(axis=1).all()
+    want = ctx.copy()
+    for i, p in enumerate(pieces):
+        trio.feed(want, i, p)
+    if ref_trio is not None:  # a sample against the reference's own SHA1Update
+        ref = ctx.copy()
+        for i in range(0, len(combos), 7):
+            ref_trio.feed(ref, i, pieces[i])
+        same_contexts(ref[::7], want[::7], "oracle against the reference")
+    data, off, ln = lay_out(pieces, [c[2] for c in combos])
+    return ctx, want, data, off, ln
+
+
+@pytest.mark.parametrize("kernel", list(KERNEL_ENVS))
+def test_seam_grid_one_call(pkg, dev, seam_grid, monkeypatch, kernel):
+    for k, v in KERNEL_ENVS[kernel].items():
+        monkeypatch.setenv(k, v)
+    ctx, want, data, off, ln = seam_grid
+    arr = DeviceArray(dev, ctx, np.random.default_rng(7))
+    device_update(pkg, dev, arr, data, off, ln)
+    same_contexts(arr.read(), want, f"seam grid, {kernel}")
+
+
+# ---- 2. streams in rounds ---------------------------------------------------
+def _streams(n):
+    rng = np.random.default_rng(300 + n)
+    lens = (rng.integers(0, 20001, n).tolist() + [0, 1, 55, 56, 63, 64, 65])[-n:]
+    msgs = [rng.integers(0, 256, L, dtype=np.uint8) for L in lens]
+    cuts = []
+    for L in lens:
+        k = int(rng.integers(1, 7))
+        edges = [0] + sorted(rng.integers(0, L + 1, k - 1).tolist()) + [L]  # equal cuts: zero-length pieces
+        cuts.append(edges)
+    off = np.zeros(n, np.uint64)
+    if n > 1:
+        off[1:] = np.cumsum([L + 3 for L in lens])[:-1]  # back to back at odd alignments
+    data = np.full(int(off[-1]) + lens[-1] + 16, PIECE_GUARD, np.uint8)
+    for m, o in zip(msgs, off):
+        data[int(o):int(o) + m.size] = m
+    return msgs, cuts, data, off
+
+
+def _rounds(cuts, off):
+    """Round r: (ids, offsets, lengths) of the messages that have an r-th piece."""
+    for r in range(6):
+        ids = np.array([i for i, e in enumerate(cuts) if len(e) - 1 > r], np.uint32)
+        if ids.size == 0:
+            return
+        o = np.array([int(off[i]) + cuts[i][r] for i in ids], np.uint64)
+        ln = np.array([cuts[i][r + 1] - cuts[i][r] for i in ids], np.uint32)
+        yield ids, o, ln
+
+
+def _after_final(trio, msgs):
+    want = trio.fresh(len(msgs))
+    for i, m in enumerate(msgs):
+        trio.feed(want, i, m)
+    dig = trio.finish(want)
+    assert all(dig[i].tobytes() == hashlib.sha1(m.tobytes()).digest() for i, m in enumerate(msgs))
+    return want, dig
+
+
+@pytest.mark.parametrize("n", [300, 1, 63, 64, 65])
+def test_streams_in_rounds_device(pkg, dev, trio, n):
+    torch = dev
+    msgs, cuts, data, off = _streams(n)
+    want, want_dig = _after_final(trio, msgs)
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        d_data = torch.from_numpy(data).cuda()
+        d_ctx = torch.full((n * 96,), GUARD, dtype=torch.uint8, device="cuda")
+        d_dig = torch.full((n, 20), GUARD, dtype=torch.uint8, device="cuda")
+        pkg.sha1chunk.init_contexts_device(d_ctx, stream=st)
+        for ids, o, ln in _rounds(cuts, off):  # a shrinking index list, all on one stream
+            pkg.sha1chunk.update_contexts_device(d_ctx, d_data, torch.from_numpy(o.view(np.int64)).cuda(),
+                                                 torch.from_numpy(ln.view(np.int32)).cuda(),
+                                                 index=torch.from_numpy(ids.view(np.int32)).cuda(), stream=st)
+        pkg.sha1chunk.final_contexts_device(d_ctx, d_dig, stream=st)
+    st.synchronize()
+    assert np.array_equal(d_dig.cpu().numpy(), want_dig)
+    same_contexts(d_ctx.cpu().numpy().view(want.dtype), want, f"{n} streams, device forms")
+
+
+@pytest.mark.parametrize("n", [300, 1, 63, 64, 65])
+def test_streams_in_rounds_host(pkg, dev, trio, n):
+    msgs, cuts, data, off = _streams(n)  # pageable numpy arrays
+    want, want_dig = _after_final(trio, msgs)
+    ctx = pkg.sha1chunk.new_contexts(n)
+    ctx["buffer"] = GUARD
+    for ids, o, ln in _rounds(cuts, off):
+        pkg.sha1chunk.update_batch(ctx, data, o, ln, index=ids)
+    dig = pkg.sha1chunk.final_batch(ctx)
+    assert np.array_equal(dig, want_dig)
+    same_contexts(ctx, want, f"{n} streams, host form")
+
+
+# ---- 3. AUTO's real selection beyond two groups per CU ----------------------
+def test_auto_beyond_two_groups_per_cu(pkg, dev, trio):
+    """32833 entries: 514 groups of 64, the smallest count that leaves the
+    split shapes on 256 CUs."""
+    torch = dev
+    n = 32833
+    rng = np.random.default_rng(32833)
+    ln = rng.integers(0, 301, n).astype(np.uint32)
+    staged = (np.arange(n) % 5 == 0) * rng.integers(1, 64, n)
+    off = np.zeros(n, np.uint64)
+    off[1:] = np.cumsum(ln.astype(np.uint64) + 1)[:-1]
+    data = rng.integers(0, 256, int(off[-1]) + int(ln[-1]) + 16, dtype=np.uint8)
+    ctx = trio.fresh(n)
+    for i in np.flatnonzero(staged):
+        trio.feed(ctx, i, rng.integers(0, 256, staged[i], dtype=np.uint8))
+    want = ctx.copy()
+    for i in range(n):
+        trio.feed(want, i, data[int(off[i]):int(off[i]) + int(ln[i])])
+    mid = want.copy()
+    want_dig = trio.finish(want)
+    d_ctx = torch.from_numpy(ctx.view(np.uint8)).cuda()
+    d_dig = torch.zeros((n, 20), dtype=torch.uint8, device="cuda")
+    pkg.sha1chunk.update_contexts_device(d_ctx, torch.from_numpy(data).cuda(), torch.from_numpy(off.view(np.int64)).cuda(),
+                                         torch.from_numpy(ln.view(np.int32)).cuda())
+    torch.cuda.synchronize()
+    same_contexts(d_ctx.cpu().numpy().view(ctx.dtype), mid, "32833 entries, after update")
+    pkg.sha1chunk.final_contexts_device(d_ctx, d_dig)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_dig.cpu().numpy(), want_dig)
+    same_contexts(d_ctx.cpu().numpy().view(ctx.dtype), want, "32833 entries, after final")
+
+
+# ---- 4. long bulk -----------------------------------------------------------
+@pytest.fixture(scope="module")
+def long_bulk(trio):
+    n = 130
+    rng = np.random.default_rng(130)
+    ctx = trio.fresh(n)
+    pieces, starts = [], []
+    for i in range(n):
+        b = (i * 29 + 1) % 64
+        trio.feed(ctx, i, rng.integers(0, 256, b + 64 * (i % 3), dtype=np.uint8))
+        k, r = i * 300 // (n - 1), (i * 37) % 64
+        pieces.append(rng.integers(0, 256, (64 - b) + 64 * k + r, dtype=np.uint8))
+        starts.append((i * 7 + 1) % 16)
+    want = ctx.copy()
+    for i, p in enumerate(pieces):
+        trio.feed(want, i, p)
+    return (ctx, want) + lay_out(pieces, starts)
+
+
+@pytest.mark.parametrize("kernel", ["auto", "fused", "unit1", "unit11", "lane"])
+def test_long_bulk(pkg, dev, long_bulk, monkeypatch, kernel):
+    """Pieces of (64 - b) + 64 k + r bytes, k up to 300: the 128-byte stage
+    loads and the prefetch of the fused and split bodies in update mode."""
+    for k, v in KERNEL_ENVS[kernel].items():
+        monkeypatch.setenv(k, v)
+    ctx, want, data, off, ln = long_bulk
+    arr = DeviceArray(dev, ctx, np.random.default_rng(11))
+    device_update(pkg, dev, arr, data, off, ln)
+    same_contexts(arr.read(), want, f"long bulk, {kernel}")
+
+
+# ---- 5. bit count -----------------------------------------------------------
+def test_bit_count_carry_and_padding(pkg, dev, trio):
+    """Fabricated contexts a few blocks below 2^32 and 2^35 bits: the carry
+    into totalLength's high word on an update of 200 bytes, then the 64-bit
+    length in final's padding."""
+    torch = dev
+    rng = np.random.default_rng(35)
+    totals = [(1 << e) - 8 * k for e in (32, 35) for k in (1, 17, 64, 65, 100, 129, 199, 200, 201, 256)]
+    n = len(totals)
+    ctx = trio.fresh(n)
+    ctx["totalLength"] = totals
+    ctx["hash"] = rng.integers(0, 1 << 32, (n, 5), dtype=np.uint64).astype(np.uint32)
+    ctx["bufferLength"] = (np.array(totals, np.uint64) // 8 % 64).astype(np.uint32)
+    ctx["buffer"] = rng.integers(0, 256, (n, 64), dtype=np.uint8)
+    pieces = [rng.integers(0, 256, 200, dtype=np.uint8) for _ in range(n)]
+    data, off, ln = lay_out(pieces, [i % 16 for i in range(n)])
+    want = ctx.copy()
+    for i, p in enumerate(pieces):
+        trio.feed(want, i, p)
+    assert (want["totalLength"] >> np.uint64(32) != ctx["totalLength"] >> np.uint64(32)).any()
+    arr = DeviceArray(dev, ctx, rng)
+    device_update(pkg, dev, arr, data, off, ln)
+    same_contexts(arr.read(), want, "update across 2^32 / 2^35 bits")
+    want_dig = trio.finish(want)
+    d_dig = torch.zeros((n, 20), dtype=torch.uint8, device="cuda")
+    pkg.sha1chunk.final_contexts_device(arr.array, d_dig, index=arr.d_index, n_contexts=arr.slots)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_dig.cpu().numpy(), want_dig)
+    same_contexts(arr.read(), want, "final across 2^32 / 2^35 bits")
+
+
+# ---- 6. migration -----------------------------------------------------------
+def test_migration_between_the_trio_and_the_batch_calls(pkg, dev):
+    """A context moves between the library's SHA1Update / SHA1Final and the
+    batch calls by plain copy (under the suite's pin: the trio on the kernels)."""
+    rng = np.random.default_rng(6)
+    lens = [0, 1, 63, 64, 65, 200, 1000, 5000]
+    n = len(lens)
+    first = [rng.integers(0, 256, L, dtype=np.uint8) for L in lens]
+    second = [rng.integers(0, 256, L, dtype=np.uint8) for L in reversed(lens)]
+    want = [hashlib.sha1(a.tobytes() + b.tobytes()).digest() for a, b in zip(first, second)]
+    data, off, ln = lay_out(second, [5] * n)
+    # the trio first, continued by update_batch, finished by SHA1Final
+    objs = [pkg.SHA1().update(a.tobytes()) for a in first]
+    ctx = np.zeros(n, pkg.sha1chunk.CONTEXT_DTYPE)
+    for i, o in enumerate(objs):
+        C.memmove(ctx.ctypes.data + 96 * i, C.addressof(o.ctx), 96)
+    pkg.sha1chunk.update_batch(ctx, data, off, ln)
+    for i, o in enumerate(objs):
+        C.memmove(C.addressof(o.ctx), ctx.ctypes.data + 96 * i, 96)
+    assert [o.final() for o in objs] == want
+    # the reverse: update_batch first, continued by SHA1Update, finished by final_batch
+    data1, off1, ln1 = lay_out(first, [9] * n)
+    ctx = pkg.sha1chunk.new_contexts(n)
+    pkg.sha1chunk.update_batch(ctx, data1, off1, ln1)
+    objs = [pkg.SHA1() for _ in range(n)]
+    for i, o in enumerate(objs):
+        C.memmove(C.addressof(o.ctx), ctx.ctypes.data + 96 * i, 96)
+        o.update(second[i].tobytes())
+        C.memmove(ctx.ctypes.data + 96 * i, C.addressof(o.ctx), 96)
+    assert [d.tobytes() for d in pkg.sha1chunk.final_batch(ctx)] == want
+
+
+# ---- 7. skips and refusals on the device -------------------------------------
+def test_device_skips(pkg, dev, trio):
+    """Entries whose index is outside the array, or whose context claims 64 or
+    2^32 - 1 staged bytes, change nothing and write no digest; their
+    neighbours are right."""
+    torch = dev
+    rng = np.random.default_rng(77)
+    n, nc = 70, 80
+    index = rng.permutation(nc)[:n].astype(np.uint32)
+    out_of_range = {3: nc, 20: nc + 1, 64: 0xFFFFFFFF, 69: 1 << 31}
+    for e, v in out_of_range.items():
+        index[e] = v
+    ctx = np.zeros(nc, pkg.sha1chunk.CONTEXT_DTYPE)
+    ctx[:] = trio.fresh(1)[0]
+    ctx["buffer"] = GUARD
+    for i in range(nc):
+        trio.feed(ctx, i, rng.integers(0, 256, i % 64, dtype=np.uint8))
+    overfull = {int(index[5]): 64, int(index[40]): 0xFFFFFFFF, int(index[65]): 100}
+    for c, v in overfull.items():
+        ctx["bufferLength"][c] = v
+    pieces = [rng.integers(0, 256, 30 + 11 * i, dtype=np.uint8) for i in range(n)]
+    data, off, ln = lay_out(pieces, [i % 16 for i in range(n)])
+    skipped = set(out_of_range) | {5, 40, 65}
+    want = ctx.copy()
+    for e in range(n):
+        if e not in skipped:
+            trio.feed(want, int(index[e]), pieces[e])
+    d_ctx = torch.from_numpy(ctx.view(np.uint8)).cuda()
+    d_index = torch.from_numpy(index.view(np.int32)).cuda()
+    d_dig = torch.full((n, 20), GUARD, dtype=torch.uint8, device="cuda")
+    pkg.sha1chunk.update_contexts_device(d_ctx, torch.from_numpy(data).cuda(), torch.from_numpy(off.view(np.int64)).cuda(),
+                                         torch.from_numpy(ln.view(np.int32)).cuda(), index=d_index)
+    torch.cuda.synchronize()
+    got = d_ctx.cpu().numpy().view(ctx.dtype)
+    live = np.array(sorted(set(range(nc)) - set(overfull)))
+    same_contexts(got[live], want[live], "neighbours of skipped entries, after update")
+    for c in overfull:
+        assert got[c].tobytes() == ctx[c].tobytes(), f"context {c} with bufferLength {overfull[c]} was touched"
+    want_dig = np.full((n, 20), GUARD, np.uint8)
+    for e in range(n):
+        if e not in skipped:
+            c = int(index[e])
+            one = want[c:c + 1]
+            want_dig[e] = trio.finish(one)[0]
+    pkg.sha1chunk.final_contexts_device(d_ctx, d_dig, index=d_index)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_dig.cpu().numpy(), want_dig), "a skipped entry's digest was written, or a neighbour's is wrong"
+    got = d_ctx.cpu().numpy().view(ctx.dtype)
+    same_contexts(got[live], want[live], "neighbours of skipped entries, after final")
+    for c in overfull:
+        assert got[c].tobytes() == ctx[c].tobytes()
+    # init skips by index too
+    pkg.sha1chunk.init_contexts_device(d_ctx, index=d_index)
+    torch.cuda.synchronize()
+    got = d_ctx.cpu().numpy().view(ctx.dtype)
+    listed = sorted(int(index[e]) for e in range(n) if e not in out_of_range)
+    assert (got["totalLength"][listed] == 0).all() and (got["bufferLength"][listed] == 0).all()
+    assert (got["hash"][listed] == np.array(IV, np.uint32)).all()
+    unlisted = sorted(set(range(nc)) - set(listed))
+    assert got[unlisted].tobytes() == want[unlisted].tobytes()
+
+
+class Refusals:
+    """A valid 65-entry device batch, and buffers a refused call must not touch."""
+
+    def __init__(self, pkg, torch, trio):
+        self.pkg, self.torch, self.L = pkg, torch, pkg.lib()
+        rng = np.random.default_rng(65)
+        self.n = 65
+        self.pieces = [rng.integers(0, 256, 77 + i, dtype=np.uint8) for i in range(self.n)]
+        data, off, ln = lay_out(self.pieces, [i % 16 for i in range(self.n)])
+        self.data = torch.from_numpy(data).cuda()
+        self.off = torch.from_numpy(off.view(np.int64)).cuda()
+        self.len = torch.from_numpy(ln.view(np.int32)).cuda()
+        self.ctx0 = trio.fresh(self.n)
+        self.ctx = torch.from_numpy(self.ctx0.view(np.uint8)).cuda()
+        self.dig = torch.full((self.n * 20 + 64,), GUARD, dtype=torch.uint8, device="cuda")
+        self.want = np.array([np.frombuffer(hashlib.sha1(p.tobytes()).digest(), np.uint8) for p in self.pieces])
+        self.st = torch.cuda.current_stream().cuda_stream
+
+    def untouched(self):
+        self.torch.cuda.synchronize()
+        assert (self.dig.cpu().numpy() == GUARD).all(), "a refused call wrote to its digest buffer"
+        assert self.ctx.cpu().numpy().tobytes() == self.ctx0.tobytes(), "a refused call wrote to the contexts"
+
+    def valid_call_is_right(self):
+        ctx = self.ctx.clone()
+        dig = self.torch.zeros((self.n, 20), dtype=self.torch.uint8, device="cuda")
+        self.pkg.sha1chunk.update_contexts_device(ctx, self.data, self.off, self.len)
+        self.pkg.sha1chunk.final_contexts_device(ctx, dig)
+        self.torch.cuda.synchronize()
+        assert np.array_equal(dig.cpu().numpy(), self.want), "the valid call after a refused one is wrong"
+
+
+def _refusal_rows():
+    EINVAL, EALIGN, OK = -1, -5, 0
+    DEVICE, ALL = 1, 2
+    rows = {}
+
+    def update(x, ctx=True, base=True, off=True, ln=True, n=None):
+        return x.L.sha1chunk_update_device_async(x.ctx.data_ptr() if ctx else None, x.n, None,
+                                                 x.data.data_ptr() if base else None,
+                                                 x.off.data_ptr() if off else None,
+                                                 x.len.data_ptr() if ln else None, x.n if n is None else n, x.st)
+
+    def final(x, ctx=True, dig=0, n=None):
+        return x.L.sha1chunk_final_device_async(x.ctx.data_ptr() if ctx else None, x.n, None, x.n if n is None else n,
+                                                x.dig.data_ptr() + dig, x.st)
+
+    def update_sync(x, flags, ctx=True):
+        return x.L.sha1chunk_update_batch(x.ctx.data_ptr() if ctx else None, x.n, None, x.data.data_ptr(),
+                                          x.off.data_ptr(), x.len.data_ptr(), x.n, flags)
+
+    def final_sync(x, flags, dig=0):
+        return x.L.sha1chunk_final_batch(x.ctx.data_ptr(), x.n, None, x.n, x.dig.data_ptr() + dig, flags)
+
+    rows["update_device_async: null contexts"] = (lambda x: update(x, ctx=False), EINVAL, "null device pointer")
+    rows["update_device_async: null base"] = (lambda x: update(x, base=False), EINVAL, "null device pointer")
+    rows["update_device_async: null offsets"] = (lambda x: update(x, off=False), EINVAL, "null device pointer")
+    rows["update_device_async: null lengths"] = (lambda x: update(x, ln=False), EINVAL, "null device pointer")
+    rows["update_device_async: n = 2^32 - 1024"] = (lambda x: update(x, n=2**32 - 1024), EINVAL, "n too large")
+    rows["update_device_async: all null, n = 0"] = (
+        lambda x: update(x, ctx=False, base=False, off=False, ln=False, n=0), OK, "")
+    rows["final_device_async: null contexts"] = (lambda x: final(x, ctx=False), EINVAL, "null device pointer")
+    rows["final_device_async: digests + 1"] = (lambda x: final(x, dig=1), EALIGN, "4-byte aligned")
+    rows["final_device_async: digests + 2"] = (lambda x: final(x, dig=2), EALIGN, "4-byte aligned")
+    rows["final_device_async: n = 2^32"] = (lambda x: final(x, n=2**32), EINVAL, "n too large")
+    rows["init_device_async: null contexts"] = (
+        lambda x: x.L.sha1chunk_init_device_async(None, x.n, None, x.n, x.st), EINVAL, "null device pointer")
+    rows["init_device_async: n = 2^32"] = (
+        lambda x: x.L.sha1chunk_init_device_async(x.ctx.data_ptr(), x.n, None, 2**32, x.st), EINVAL, "n too large")
+    rows["update_batch: DEVICE, null contexts"] = (lambda x: update_sync(x, DEVICE, ctx=False), EINVAL, "null pointer")
+    rows["update_batch: ALL_DEVICES"] = (lambda x: update_sync(x, ALL), EINVAL, "SHA1CHUNK_ALL_DEVICES")
+    rows["update_batch: DEVICE | ALL_DEVICES"] = (lambda x: update_sync(x, DEVICE | ALL), EINVAL,
+                                                  "SHA1CHUNK_ALL_DEVICES")
+    rows["final_batch: ALL_DEVICES"] = (lambda x: final_sync(x, ALL), EINVAL, "SHA1CHUNK_ALL_DEVICES")
+    rows["final_batch: DEVICE, digests + 2"] = (lambda x: final_sync(x, DEVICE, dig=2), EALIGN, "4-byte aligned")
+    return rows
+
+
+REFUSAL_ROWS = _refusal_rows()
+
+
+@pytest.fixture(scope="module")
+def refusals(pkg, dev, trio):
+    x = Refusals(pkg, dev, trio)
+    x.valid_call_is_right()
+    return x
+
+
+@pytest.mark.parametrize("row", list(REFUSAL_ROWS))
+def test_refused_on_the_host(refusals, row):
+    call, code, text = REFUSAL_ROWS[row]
+    x = refusals
+    assert x.L.sha1chunk_device_pci_bus_id(0, None, 0) == x.pkg.EINVAL  # a marker a refusal must replace
+    got = call(x)
+    err = x.L.sha1chunk_last_error().decode()
+    assert got == code, (got, err)
+    if code:
+        assert text in err, err
+    x.untouched()
+    x.valid_call_is_right()
+
+
+def test_sync_device_form(pkg, dev, trio):
+    """SHA1CHUNK_DEVICE: the async form and a wait."""
+    x = Refusals(pkg, dev, trio)
+    ctx = x.ctx.clone()
+    dig = dev.zeros((x.n, 20), dtype=dev.uint8, device="cuda")
+    L = pkg.lib()
+    dev.cuda.synchronize()  # the uploads above: the calls run on the library's own stream
+    assert L.sha1chunk_update_batch(ctx.data_ptr(), x.n, None, x.data.data_ptr(), x.off.data_ptr(), x.len.data_ptr(),
+                                    x.n, 1) == 0, L.sha1chunk_last_error()
+    assert L.sha1chunk_final_batch(ctx.data_ptr(), x.n, None, x.n, dig.data_ptr(), 1) == 0, L.sha1chunk_last_error()
+    assert np.array_equal(dig.cpu().numpy(), x.want)  # no synchronize: the calls waited (cpu() copies on the legacy stream)
+
+
+# ---- 8. host form over several fills ---------------------------------------
+_FILLS_CHILD = r"""
+import hashlib, importlib, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+pkg = importlib.import_module("congestion-control-with-bittorren_amd")
+pkg.set_device(0)
+rng = np.random.default_rng(8)
+lens = [int(x) for x in rng.integers(0, 70000, 20)] + [3 * 1024 * 1024 + 17] + [int(x) for x in rng.integers(0, 70000, 20)]
+off = np.zeros(len(lens), np.uint64)
+off[1:] = np.cumsum([L + 5 for L in lens])[:-1]
+data = rng.integers(0, 256, int(off[-1]) + lens[-1], dtype=np.uint8)
+index = rng.permutation(50)[:len(lens)].astype(np.uint32)
+ctx = pkg.sha1chunk.new_contexts(50)
+spare = ctx.copy()
+pkg.sha1chunk.update_batch(ctx, data, off, np.array(lens, np.uint32), index=index)
+listed = np.zeros(50, bool); listed[index] = True
+assert ctx[~listed].tobytes() == spare[~listed].tobytes(), "an unlisted context changed"
+dig = pkg.sha1chunk.final_batch(ctx, index=index)
+for i, L in enumerate(lens):
+    want = hashlib.sha1(data[int(off[i]):int(off[i]) + L].tobytes()).digest()
+    assert dig[i].tobytes() == want, (i, L)
+print("several fills ok")
+"""
+
+
+def test_host_form_over_several_fills():
+    """SHA1CHUNK_UPDATE_FILL_MIB=1: a 3 MiB + 17 byte piece, cut inside the
+    library, beside 40 small ones in several fills."""
+    env = dict(os.environ, SHA1CHUNK_UPDATE_FILL_MIB="1")
+    r = subprocess.run([sys.executable, "-c", _FILLS_CHILD, ROOT], capture_output=True, text=True, env=env, cwd=ROOT,
+                       timeout=120)
+    assert r.returncode == 0 and "several fills ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+
+
+def test_migration_with_the_trio_on_the_host():
+    """The same migration with the library's default routing and a host-small
+    threshold: SHA1Update / SHA1Final on the host, the batch calls on the
+    kernels (SHA1CHUNK_HOST_SMALL does not apply to them)."""
+    code = r"""
+import ctypes as C, hashlib, importlib, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+pkg = importlib.import_module("congestion-control-with-bittorren_amd")
+pkg.set_device(0)
+a, b = bytes(range(200)) * 3, bytes(range(255, 0, -1)) * 5
+o = pkg.SHA1().update(a)
+ctx = np.zeros(1, pkg.sha1chunk.CONTEXT_DTYPE)
+C.memmove(ctx.ctypes.data, C.addressof(o.ctx), 96)
+pkg.sha1chunk.update_batch(ctx, b, [0], [len(b)])
+C.memmove(C.addressof(o.ctx), ctx.ctypes.data, 96)
+assert o.final() == hashlib.sha1(a + b).digest()
+ctx = pkg.sha1chunk.new_contexts(1)
+pkg.sha1chunk.update_batch(ctx, a, [0], [len(a)])
+o = pkg.SHA1()
+C.memmove(C.addressof(o.ctx), ctx.ctypes.data, 96)
+o.update(b)
+C.memmove(ctx.ctypes.data, C.addressof(o.ctx), 96)
+assert pkg.sha1chunk.final_batch(ctx)[0].tobytes() == hashlib.sha1(a + b).digest()
+print("migration ok")
+"""
+    r = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True,
+                       env=default_env(SHA1CHUNK_HOST_SMALL="4096"), cwd=ROOT, timeout=120)
+    assert r.returncode == 0 and "migration ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
