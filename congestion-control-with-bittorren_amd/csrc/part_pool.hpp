@@ -17,11 +17,18 @@
 #include <sched.h>
 #include <string>
 #include <thread>
+#include <unistd.h>
 #include <vector>
 
 namespace s1host {
 
 inline void cpu_relax() { __builtin_ia32_pause(); }
+
+// The CPUs the process may run on: its main thread's (the thread-group
+// leader's) affinity mask, not the calling thread's -- a receive thread
+// pinned to one L3 domain (sha1chunk_receive_cpus) asks on behalf of the
+// process, and the helper threads it creates must not inherit its few CPUs.
+inline bool process_cpus(cpu_set_t* out) { return sched_getaffinity(getpid(), sizeof *out, out) == 0; }
 
 // Persistent helper threads that run the parts of one job (a host copy
 // split in pieces, a file read split over pread calls) together with the
@@ -33,13 +40,23 @@ class PartPool {
 public:
     // cpus (optional): the helpers run on these host CPUs only -- the ones
     // near the GPU whose pinned buffers they fill (rt_device.hip
-    // near_cpus); the calling thread's own placement is the caller's
+    // near_cpus); without it, on the process's CPUs (process_cpus), never
+    // on the mask they would inherit from a pinned creator.  The calling
+    // thread's own placement is the caller's.  The helpers are named
+    // "s1pool" (/proc/<pid>/task/*/comm); both are done before this returns.
     explicit PartPool(int helpers, const cpu_set_t* cpus = nullptr) {
-        if (cpus) {
-            cpus_ = *cpus;
-            pin_ = true;
+        cpu_set_t set;
+        bool pin = true;
+        if (cpus)
+            set = *cpus;
+        else
+            pin = process_cpus(&set);
+        for (int i = 0; i < helpers; ++i) {
+            th_.emplace_back([this] { loop(); });
+            const pthread_t t = th_.back().native_handle();
+            if (pin) (void)pthread_setaffinity_np(t, sizeof set, &set);
+            (void)pthread_setname_np(t, "s1pool");
         }
-        for (int i = 0; i < helpers; ++i) th_.emplace_back([this] { loop(); });
     }
     ~PartPool() {
         {
@@ -97,7 +114,6 @@ private:
         }
     }
     void loop() {
-        if (pin_) (void)pthread_setaffinity_np(pthread_self(), sizeof cpus_, &cpus_);
         uint64_t seen = 0;
         for (;;) {
             int spin = 0;
@@ -123,8 +139,6 @@ private:
         }
     }
     std::vector<std::thread> th_;
-    cpu_set_t cpus_{};
-    bool pin_ = false;
     std::mutex mu_;
     std::condition_variable cv_, done_;
     std::atomic<uint64_t> gen_{0};

@@ -93,8 +93,8 @@ void probe() {
 
 namespace s1rt {
 // Host CPUs near HIP device `id`: the CPUs of its NUMA node within this
-// process's affinity mask.  The library's helper threads -- the pageable-
-// batch packing, the file pipeline's preads into pinned slots, the verify
+// process's affinity mask (s1host::process_cpus).  The library's helper
+// threads -- the pageable-batch packing, the file pipeline's preads into pinned slots, the verify
 // queue's split copies when asked for (SHA1CHUNK_VQ_THREADS) -- run there,
 // beside the pinned memory they write (hipHostMalloc already places it on
 // the GPU's node: profiles/vq_place_r06*.jsonl) and the GPU that reads it.
@@ -112,8 +112,10 @@ const cpu_set_t* near_cpus(int id) {
     Near& n = near[id];
     std::call_once(n.once, [&] {
         if (numa_off()) return;
+        // the process's CPUs, not the calling thread's: the set is cached for
+        // the process, and the first caller may be a pinned receive thread
         cpu_set_t allowed, mine;
-        if (sched_getaffinity(0, sizeof allowed, &allowed) != 0) return;
+        if (!s1host::process_cpus(&allowed)) return;
         // nothing to gain when every allowed CPU is on this node already,
         // and no piling of a pool's helpers onto fewer than kMinNearCpus
         constexpr int kMinNearCpus = 4;
@@ -139,8 +141,8 @@ const std::vector<cpu_set_t>& receive_domains(int id) {
     if (id < 0 || id >= 64) return none;
     Dom& d = doms[id];
     std::call_once(d.once, [&] {
-        cpu_set_t allowed, base;
-        if (sched_getaffinity(0, sizeof allowed, &allowed) != 0) return;
+        cpu_set_t allowed, base;  // the process's CPUs, as in near_cpus
+        if (!s1host::process_cpus(&allowed)) return;
         if (numa_off() || device_node_cpus(id, allowed, &base) == 0) base = allowed;
         s1host::l3_domains(base, &d.dom, [](int cpu) {
             char path[128];

@@ -79,6 +79,15 @@ struct PvqRegion {
     bool collected;
     bool released;
     std::thread::id owner;  // the thread that allocated it (reserve or submit)
+    bool polled = false;    // poll() handed its result out: what is left is its owner's release()
+};
+// A collected result waiting for poll(), with its region's id (a copied
+// chunk's region may be freed, its id below reg_base, before the result is
+// popped).
+struct PvqResult {
+    uint64_t tag;
+    uint8_t mismatch;
+    uint64_t region;
 };
 }  // namespace
 
@@ -123,7 +132,7 @@ struct Pvq {
     uint64_t next_g = 0;
     std::deque<PvqGroup> groups;  // published, oldest first
     size_t inflight = 0;          // published, not yet collected
-    std::deque<std::pair<uint64_t, uint8_t>> ready;
+    std::deque<PvqResult> ready;
     size_t pending = 0;
     // two launch slots, each a stream, an alive-word set and the event of
     // its last drain; a slot is reused only once that drain has ended
@@ -375,7 +384,7 @@ int pvq_reap(Pvq* P) {
         unfinished = 0;
         for (uint32_t j = 0; j < G.count; ++j) {
             const uint64_t sl = (G.slot0 + j) % P->nslots;
-            P->ready.emplace_back(P->tags[sl], P->res[sl]);
+            P->ready.push_back(PvqResult{P->tags[sl], P->res[sl], P->slot_reg[sl]});
             P->regions[P->slot_reg[sl] - P->reg_base].collected = true;
         }
         G.collected = true;
@@ -395,7 +404,9 @@ int pvq_reap(Pvq* P) {
 // An open group is published first (its chunks hold ring space too), and a
 // wait that only the caller can end -- the oldest region of the data ring
 // is a reserved buffer not yet committed, or collected and not released --
-// fails at once when `stuck` says so.
+// fails at once when `stuck(false)` says so.  When the bound runs out,
+// `stuck(true)` may still name a caller's buffer as what holds the room
+// (ENOMEM); otherwise the drain is what did not progress (EHIP).
 // Bound on any one wait (SHA1CHUNK_VQ_WAIT_S, default 120 s).
 std::chrono::seconds pvq_wait_bound() {
     static const std::chrono::seconds b(std::max<uint64_t>(1, env_u64("SHA1CHUNK_VQ_WAIT_S", 120)));
@@ -410,12 +421,12 @@ int pvq_wait(Pvq* P, Pred pred, const char* what, Stuck stuck) {
         if ((rc = pvq_reap(P))) return rc;
         if (pred()) return SHA1CHUNK_OK;
         if (P->open_count && (rc = pvq_publish(P))) return rc;
-        if (const char* why = stuck())
+        const bool expired = std::chrono::steady_clock::now() - t0 > pvq_wait_bound();
+        if (const char* why = stuck(expired))
             return fail(SHA1CHUNK_ENOMEM, "vq: %s: the ring's oldest region is %s (%zu reserved buffers held)", what,
                         why, P->held.size());
         if (P->inflight && (rc = pvq_ensure_drain(P))) return rc;
-        if (std::chrono::steady_clock::now() - t0 > pvq_wait_bound())
-            return fail(SHA1CHUNK_EHIP, "vq: %s timed out (drain not progressing)", what);
+        if (expired) return fail(SHA1CHUNK_EHIP, "vq: %s timed out (drain not progressing)", what);
         ++P->n_sleeps;
         // sleep without the queue's lock: the other threads' commits, polls
         // and releases are what frees the ring (each call re-checks its state
@@ -429,7 +440,7 @@ int pvq_wait(Pvq* P, Pred pred, const char* what, Stuck stuck) {
 }
 template <typename Pred>
 int pvq_wait(Pvq* P, Pred pred, const char* what) {
-    return pvq_wait(P, pred, what, [] { return static_cast<const char*>(nullptr); });
+    return pvq_wait(P, pred, what, [](bool) { return static_cast<const char*>(nullptr); });
 }
 
 // Queues alive at process exit (a caller that never destroys its queue):
@@ -669,20 +680,27 @@ int pvq_alloc(Pvq* P, uint32_t len, bool reserved, uint64_t* id) {
     // The wait is hopeless when the ring's head is
     //  * the caller's own reservation, not committed (this thread cannot
     //    commit it while it waits here), or
-    //  * a reserved buffer whose result is finished but that is not released,
-    //    whoever holds it: only a poll() that hands out the result and the
-    //    release() after it free that room.  When every receive thread sits in
-    //    reserve() nobody polls, so after a short grace (another thread may be
-    //    polling and releasing right now) the call fails and its caller polls
-    //    and releases (round 6: four receive threads all waiting here stalled
-    //    for the whole 120 s bound).
+    //  * the caller's own verified buffer, not released, its result polled
+    //    or not (this thread cannot release it while it waits here), or
+    //  * another thread's verified buffer whose result is still unpolled:
+    //    only a poll() that hands out the result and the release() after it
+    //    free that room.  When every receive thread sits in reserve() nobody
+    //    polls, so after a short grace (another thread may be polling and
+    //    releasing right now) the call fails and its caller polls and
+    //    releases (round 6: four receive threads all waiting here stalled for
+    //    the whole 120 s bound).
     // Another thread's reservation not yet committed is a session still
-    // filling, which that thread will commit: the call waits for
-    // it as for any in-flight group (bounded, pvq_wait).
+    // filling, which that thread will commit, and another
+    // thread's verified buffer whose result poll() has handed out is being
+    // copied into its owner's job buffer, which that thread will release
+    // (no poll() of the caller's could free it): the call waits
+    // for either as for any in-flight group (bounded, pvq_wait).  If the
+    // bound runs out on such a polled buffer the call fails with ENOMEM and
+    // names it: the drain is fine, the room is a caller's to free.
     const std::thread::id me = std::this_thread::get_id();
     std::chrono::steady_clock::time_point held_since{};
     uint64_t held_id = ~0ull;  // the head region the grace is running for
-    auto stuck = [&]() -> const char* {
+    auto stuck = [&](bool expired) -> const char* {
         if (P->regions.empty()) return nullptr;
         const PvqRegion& r = P->regions.front();
         if (!r.reserved || r.released) return nullptr;
@@ -690,6 +708,10 @@ int pvq_alloc(Pvq* P, uint32_t len, bool reserved, uint64_t* id) {
         if (!r.committed) return r.owner == me ? own : nullptr;
         if (!r.collected) return nullptr;
         if (r.owner == me) return own;
+        if (r.polled)
+            return expired ? "another thread's verified buffer, its result polled and not released within "
+                             "SHA1CHUNK_VQ_WAIT_S (that thread's release() frees it)"
+                           : nullptr;
         const auto now = std::chrono::steady_clock::now();
         if (held_id != P->reg_base) {  // a new head region: its own grace
             held_id = P->reg_base;
@@ -825,8 +847,11 @@ long pvq_poll(Pvq* P, uint64_t* tags, uint8_t* mismatch, size_t max, int wait) {
     }
     size_t n = 0;
     while (n < max && !P->ready.empty()) {
-        tags[n] = P->ready.front().first;
-        mismatch[n] = P->ready.front().second;
+        const PvqResult& r = P->ready.front();
+        tags[n] = r.tag;
+        mismatch[n] = r.mismatch;
+        // a copied chunk's region may be freed already (its id below reg_base)
+        if (r.region >= P->reg_base) P->regions[r.region - P->reg_base].polled = true;
         P->ready.pop_front();
         ++n;
     }

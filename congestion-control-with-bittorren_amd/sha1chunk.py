@@ -155,10 +155,13 @@ def _one_hip_runtime() -> None:
     torch sees no device (tools/order_probe.py, profiles/order_probe_r06.log).
     So where PyTorch is installed it is imported first, which maps its
     runtime without starting it (the host-routed calls still never open
-    /dev/kfd: tests/test_host_small.py)."""
+    /dev/kfd: tests/test_host_small.py).  A PyTorch that is installed but
+    fails to import (OSError for a missing shared object, RuntimeError) is as
+    good as none: the library then brings its own runtime, and the host-only
+    calls (binary2hex ...) need none at all."""
     try:
         import torch  # noqa: F401
-    except ImportError:
+    except Exception:  # noqa: BLE001 -- whatever a broken install raises
         pass
 
 

@@ -249,15 +249,23 @@ int sha1chunk_vq_submit(sha1chunk_vq *q, const void *chunk, uint32_t len,
  * reservation may also be released without a commit.  Unreleased buffers
  * hold ring space.  reserve() and submit() wait (bounded, SHA1CHUNK_VQ_WAIT_S,
  * default 120 s) for room while in-flight chunks or other threads'
- * reservations still filling hold it; they fail (NULL, resp.
- * SHA1CHUNK_ENOMEM) rather than wait when the ring's oldest region is the
- * calling thread's own reservation, not committed or not released -- room
- * only that thread could free -- or, after a 2 ms grace, any thread's
- * verified buffer whose result nobody has polled and released yet (room only
- * a poll() and release() free: when every receive thread waits in reserve()
- * nobody polls).  On NULL, poll, release and retry.  In batch mode and
- * on the batch-1 host path the buffer is ordinary host memory (commit
- * copies it, resp. hashes it in place). */
+ * reservations still filling hold it.  When the ring's oldest region is a
+ * reserved buffer that is verified and not released, one of three things
+ * happens:
+ *  - it is the calling thread's own (its result polled or not; likewise its
+ *    own reservation not yet committed): the call fails at once (NULL, resp.
+ *    SHA1CHUNK_ENOMEM) -- room only that thread could free;
+ *  - it is another thread's and its result is still unpolled: the call fails
+ *    the same way after a 2 ms grace (room only a poll() and the release()
+ *    after it free: when every receive thread waits in reserve() nobody
+ *    polls).  Poll, release and retry;
+ *  - it is another thread's and poll() has handed its result out: its owner
+ *    is copying the chunk out and will release it, so the call waits for
+ *    that release() like for an in-flight chunk.  If the bound runs out
+ *    first the call fails with SHA1CHUNK_ENOMEM ("polled and not released"),
+ *    not SHA1CHUNK_EHIP: the drain is fine.
+ * In batch mode and on the batch-1 host path the buffer is ordinary host
+ * memory (commit copies it, resp. hashes it in place). */
 void *sha1chunk_vq_reserve(sha1chunk_vq *q, uint32_t len);
 int sha1chunk_vq_commit(sha1chunk_vq *q, void *buf, uint32_t len, const uint8_t expected[20],
                         uint64_t tag);
@@ -501,7 +509,8 @@ int sha1chunk_device_pci_bus_id(int device, char *buf, size_t len);
 /* Where a receive thread feeding a verify queue on `device` should run:
  * writes into `mask` (a Linux cpu_set_t, len >= sizeof(cpu_set_t); the rest
  * of len is zeroed) the CPUs of one L3 domain (one CCD on the MI355X boxes'
- * EPYC hosts) of the device's NUMA node, within the caller's affinity mask;
+ * EPYC hosts) of the device's NUMA node, within the process's affinity mask
+ * (its main thread's, whichever thread calls, pinned or not);
  * receive thread `slot` gets domain slot mod their count, so threads 0..k-1
  * land on k different domains.  *domains (if not NULL) receives that count.
  * With SHA1CHUNK_NUMA=off, or the node unknown, the domains of every allowed

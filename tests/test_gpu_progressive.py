@@ -408,3 +408,120 @@ def test_latency_after_the_last_packet(pkg, dev, fixture_files, golden):
     print(f"final advance -> verdict: progressive median {prog[2] * 1e3:.3f} ms {[round(x * 1e3, 3) for x in prog]}, "
           f"lone-chunk verify queue median {lone[2] * 1e3:.3f} ms {[round(x * 1e3, 3) for x in lone]}")
     assert prog[2] <= 0.5 * lone[2], (prog, lone)
+
+
+# ---- every instantiation of the lane kernel (SHA1CHUNK_PV_DEPTH) -----------
+# sha1_progress_kernel<DEPTH> keeps DEPTH blocks in flight per lane; where the
+# three instantiations differ is the refill index min(k + j + DEPTH, last) and
+# the mask live = k + j < nb, i.e. block counts below, at and just above the
+# depth and its multiples.
+DEPTH_BLOCKS = [0, 1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 23, 24, 25]
+DEPTH_TAILS = [0, 1, 55, 56, 63]
+DEPTH_SESSIONS = 32
+DEPTH_STRIDE = 2048
+
+
+def _depth_shapes():
+    """(whole blocks, tail bytes) of the 32 sessions: every block count, each
+    with two different tails, every tail."""
+    shapes = [(DEPTH_BLOCKS[i % 15], DEPTH_TAILS[(i + i // 15) % 5]) for i in range(DEPTH_SESSIONS)]
+    assert {b for b, _ in shapes} == set(DEPTH_BLOCKS) and {t for _, t in shapes} == set(DEPTH_TAILS)
+    assert max(64 * b + t for b, t in shapes) < DEPTH_STRIDE
+    return shapes
+
+
+@pytest.fixture(scope="module")
+def depth_corpus():
+    """The sessions' bytes and hashlib's digests of them, made once."""
+    rng = np.random.default_rng(77)
+    datas = [_bytes(rng, 64 * b + t) for b, t in _depth_shapes()]
+    return datas, [hashlib.sha1(d.tobytes()).digest() for d in datas]
+
+
+def _whole_buffer(r):
+    """The session's whole buffer, beyond the chunk's length too."""
+    import ctypes as C
+    return np.ctypeslib.as_array(C.cast(r.ptr, C.POINTER(C.c_uint8)), shape=(DEPTH_STRIDE,))
+
+
+@pytest.mark.parametrize("depth", [2, 4, 8])
+def test_every_prefetch_depth(pkg, dev, monkeypatch, depth_corpus, depth):
+    """The lane kernel at each prefetch depth: 32 sessions whose whole-block
+    counts lie below, at and above the depth and its multiples (0 .. 25) with
+    tails 0, 1, 55, 56 and 63, 0xA5 wherever the chunk's bytes are not final
+    yet.  (a) all completed by one advance_many on an idle object: one launch
+    of 32 entries, every block count in one wave; (b) two rounds, the first up
+    to 1, D - 1, D or D + 1 blocks, so that a resumed midstate meets each
+    refill edge too.  Digests and verdicts are hashlib's; one expected digest
+    per feeding is corrupted and must be flagged."""
+    monkeypatch.setenv("SHA1CHUNK_PV_KERNEL", "lane")
+    monkeypatch.setenv("SHA1CHUNK_PV_DEPTH", str(depth))
+    shapes = _depth_shapes()
+    datas, wants = depth_corpus
+    lens = [len(d) for d in datas]
+    S = DEPTH_SESSIONS
+
+    def open_all(pv, bad, tag0):
+        rs = []
+        for i in range(S):
+            exp = wants[i] if i != bad else wants[i][:7] + bytes([wants[i][7] ^ 0x20]) + wants[i][8:]
+            r = pv.open(lens[i], exp, tag0 + i)
+            assert r.ptr % 128 == 0
+            _whole_buffer(r)[:] = 0xA5
+            rs.append(r)
+        return rs
+
+    def expect(bad, tag0):
+        return {tag0 + i: (1 if i == bad else 0, wants[i]) for i in range(S)}
+
+    # (a) one call, one launch, one wave
+    with pkg.ProgressiveVerifier(sessions=S, max_chunk_len=DEPTH_STRIDE) as pv:
+        st0 = pv.stats()
+        assert st0["kernel"] == "lane" and st0["depth"] == depth and st0["launches"] == 0
+        rs = open_all(pv, bad=13, tag0=100)
+        for i, r in enumerate(rs):
+            r.view[:] = datas[i]
+        assert pv.advance_many([(rs[i], lens[i]) for i in range(S)]) == S
+        st = pv.stats()
+        assert st["launches"] == st0["launches"] + 1 and st["entries"] == st0["entries"] + S, (st0, st)
+        assert st["launches_shared"] == 0 and st["depth"] == depth
+        assert st["blocks"] == st0["blocks"] + sum(b for b, _ in shapes)
+        assert _collect(pv, S) == expect(13, 100)
+        assert all(pv.hashed(rs[i]) == lens[i] for i in range(S)) and pv.pending == 0
+        for r in rs:
+            pv.close(r)
+
+    # (b) two rounds: the second resumes stored midstates
+    with pkg.ProgressiveVerifier(sessions=S, max_chunk_len=DEPTH_STRIDE) as pv:
+        rs = open_all(pv, bad=21, tag0=200)
+        ks = [1, depth - 1, depth, depth + 1]
+        first = [64 * min(ks[i % 4], shapes[i][0]) for i in range(S)]
+        assert {min(ks[i % 4], shapes[i][0]) for i in range(S)} >= set(ks)
+        one = [i for i in range(S) if first[i] > 0]
+        two = [i for i in range(S) if not (first[i] > 0 and first[i] == lens[i])]  # not complete after round one
+        assert len(one) == sum(1 for b, _ in shapes if b > 0)  # every session with a whole block
+        for i in one:
+            rs[i].view[:first[i]] = datas[i][:first[i]]
+        assert pv.advance_many([(rs[i], first[i]) for i in one]) == len(one)
+        _wait(lambda: all(pv.hashed(rs[i]) >= first[i] for i in one), "the first round's blocks")
+        for i in two:
+            assert pv.hashed(rs[i]) == first[i]
+            rs[i].view[first[i]:] = datas[i][first[i]:]
+        assert pv.advance_many([(rs[i], lens[i]) for i in two]) == len(two)
+        assert _collect(pv, S) == expect(21, 200)
+        st = pv.stats()
+        assert st["launches_shared"] == 0 and st["depth"] == depth
+        assert st["blocks"] == sum(b for b, _ in shapes)
+        assert pv.pending == 0 and pv.poll() == []
+        for r in rs:
+            pv.close(r)
+
+
+def test_bad_prefetch_depth(pkg, dev, monkeypatch):
+    """SHA1CHUNK_PV_DEPTH is read in create(): 3 is no instantiation."""
+    monkeypatch.setenv("SHA1CHUNK_PV_DEPTH", "3")
+    assert not pkg.lib().sha1chunk_pv_create(4, 4096)
+    assert b"SHA1CHUNK_PV_DEPTH" in pkg.lib().sha1chunk_last_error()
+    with pytest.raises(pkg.Sha1ChunkError) as ei:
+        pkg.ProgressiveVerifier(sessions=4, max_chunk_len=4096)
+    assert ei.value.code == pkg.sha1chunk.EINVAL and "SHA1CHUNK_PV_DEPTH" in str(ei.value)

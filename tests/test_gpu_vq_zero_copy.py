@@ -13,6 +13,7 @@ where it lies, sha1chunk_vq_release gives it back after the job-buffer copy.
 Checked against the reference's golden digests (config 2's corpus), with 20 %
 of the chunks corrupted in place, in every queue implementation."""
 import hashlib
+import json
 import os
 import subprocess
 import sys
@@ -252,6 +253,204 @@ def test_other_threads_finished_unreleased_head_fails_fast(pkg, dev, monkeypatch
         q.commit(r, dig, 500)
         assert q.poll(wait=True) == [(500, 0)]
         q.release(r)
+
+
+def _hold_polled_head(q, chunk, dig, hold, polled, releasing, errors, when, tag=10**6):
+    """A session's own thread: reserve the ring's first buffer, fill it,
+    commit, poll until its own verdict is in hand (`polled`), keep the buffer
+    for `hold` seconds -- the job-buffer copy of reliable_udp.c:696-709 --
+    and release it (`releasing` is set just before)."""
+    try:
+        r0 = q.reserve(65536)
+        r0.view[:] = np.frombuffer(chunk, np.uint8)
+        q.commit(r0, dig, tag)
+        mine = {}
+        t0 = time.monotonic()
+        while tag not in mine:
+            mine.update(q.poll(wait=True))
+            assert time.monotonic() - t0 < 30.0
+        assert mine == {tag: 0}, mine
+        when["polled"] = time.monotonic()
+        polled.set()
+        time.sleep(hold)
+        releasing.set()
+        q.release(r0)
+    except BaseException as e:  # noqa: BLE001 -- reported by the main thread
+        errors.append(repr(e))
+        polled.set()
+
+
+@pytest.mark.parametrize("call", ["submit", "reserve"])
+def test_polled_unreleased_head_makes_others_wait(pkg, dev, monkeypatch, call):
+    """the ring's head is another session's verified
+    buffer whose owner has already polled its verdict and is copying the
+    chunk out.  No poll of this thread's could free it, so its submits and
+    reserves wait (bounded) for the owner's release instead of failing with
+    ENOMEM after the 2 ms grace meant for unpolled results.  The session
+    holds its polled buffer for 0.3 s; the main thread meanwhile issues three
+    rings' worth of chunks.  Call number 128 is the first that needs the head
+    freed: it succeeds, and not before the release."""
+    monkeypatch.setenv("SHA1CHUNK_VQ_MODE", "persistent")
+    monkeypatch.setenv("SHA1CHUNK_VQ_RING_MIB", "8")  # 128 chunks of 64 KiB
+    chunk = bytes(range(256)) * 256
+    chunk_np = np.frombuffer(chunk, np.uint8)
+    dig = hashlib.sha1(chunk).digest()
+    with pkg.VerifyQueue(batch=64, max_chunk_len=65536) as q:
+        polled, releasing = threading.Event(), threading.Event()
+        errors, when, got, held = [], {}, {}, {}
+        t = threading.Thread(target=_hold_polled_head, args=(q, chunk, dig, 0.3, polled, releasing, errors, when))
+        t.start()
+
+        def collect(wait=False):
+            for tag, m in q.poll(wait=wait):
+                got[tag] = m
+                if call == "reserve":  # this thread's own buffers: released once their verdict is in
+                    q.release(held.pop(tag))
+
+        try:
+            assert polled.wait(timeout=30) and not errors, errors
+            for i in range(3 * 128):
+                exp = dig if i % 7 else bytes(20)
+                if call == "submit":
+                    q.submit(chunk, exp, i)
+                else:
+                    while len(held) >= 64:  # never this thread's own buffers that fill the ring
+                        collect(wait=True)
+                    r = q.reserve(65536)
+                if i == 127:  # the ring's 128th buffer: room only once the session's head buffer is freed
+                    since = time.monotonic() - when["polled"]
+                    print(f"call 128 ({call}) returned {since * 1e3:.1f} ms after the session's poll")
+                    assert releasing.is_set() and since >= 0.25, since
+                if call == "reserve":
+                    r.view[:] = chunk_np
+                    held[i] = r
+                    q.commit(r, exp, i)
+                collect()
+        finally:
+            t.join(timeout=60)  # destroy must not overlap the session's calls
+        assert not errors and releasing.is_set(), errors
+        while q.pending:
+            collect(wait=True)
+        assert got == {i: (0 if i % 7 else 1) for i in range(3 * 128)} and not held
+
+
+def test_own_polled_unreleased_head_fails_fast(pkg, dev, monkeypatch):
+    """The other side of the rule above: the calling thread's own verified
+    buffer at the ring's head, its verdict polled and the buffer kept, is
+    room only this thread could free, so the submit that needs it fails at
+    once (no wait for a release that cannot come) and names the thread's own
+    buffer; after the release the same submit goes through."""
+    monkeypatch.setenv("SHA1CHUNK_VQ_MODE", "persistent")
+    monkeypatch.setenv("SHA1CHUNK_VQ_RING_MIB", "8")  # 128 chunks of 64 KiB
+    chunk = bytes(range(256)) * 256
+    dig = hashlib.sha1(chunk).digest()
+    with pkg.VerifyQueue(batch=64, max_chunk_len=65536) as q:
+        r0 = q.reserve(65536)
+        r0.view[:] = np.frombuffer(chunk, np.uint8)
+        q.commit(r0, dig, 10**6)
+        got = dict(q.poll(wait=True))
+        assert got == {10**6: 0}
+        for i in range(127):  # the rest of the ring
+            q.submit(chunk, dig if i % 7 else bytes(20), i)
+        t0 = time.monotonic()
+        with pytest.raises(pkg.Sha1ChunkError) as ei:
+            q.submit(chunk, bytes(20), 127)
+        secs = time.monotonic() - t0
+        print(f"own polled head: submit refused after {secs * 1e3:.1f} ms")
+        assert secs < 5.0
+        assert ei.value.code == pkg.sha1chunk.ENOMEM and "this thread's own reserved buffer" in str(ei.value)
+        assert np.array_equal(r0.view, np.frombuffer(chunk, np.uint8))  # still the verified chunk
+        q.release(r0)
+        q.submit(chunk, bytes(20), 127)
+        while q.pending:
+            got.update(q.poll(wait=True))
+        want = {i: (0 if i % 7 else 1) for i in range(127)}
+        want.update({127: 1, 10**6: 0})
+        assert got == want
+
+
+_WAIT_BOUND_CHILD = r"""
+import hashlib, importlib, json, sys, threading, time
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+# no PyTorch in this process (its import is most of a start-up): the library
+# then brings its own HIP runtime, as it does for a C caller
+sys.modules["torch"] = None
+pkg = importlib.import_module("congestion-control-with-bittorren_amd")
+pkg.set_device(0)
+chunk = bytes(range(256)) * 256
+dig = hashlib.sha1(chunk).digest()
+TAG = 10**6
+out, got, errors = {"failed_at": None}, {}, []
+with pkg.VerifyQueue(batch=64, max_chunk_len=65536) as q:
+    polled, released = threading.Event(), threading.Event()
+
+    def session():
+        try:
+            r0 = q.reserve(65536)
+            r0.view[:] = np.frombuffer(chunk, np.uint8)
+            q.commit(r0, dig, TAG)
+            mine = {}
+            while TAG not in mine:
+                mine.update(q.poll(wait=True))
+            got.update(mine)
+            polled.set()
+            time.sleep(3.0)
+            q.release(r0)
+        except BaseException as e:
+            errors.append(repr(e))
+            polled.set()
+        released.set()
+
+    t = threading.Thread(target=session)
+    t.start()
+    try:
+        assert polled.wait(timeout=30) and not errors, errors
+        i = 0
+        while i < 3 * 128:
+            t0 = time.monotonic()
+            try:
+                q.submit(chunk, dig if i % 7 else bytes(20), i)
+            except pkg.Sha1ChunkError as e:
+                assert out["failed_at"] is None, ("refused twice", i, str(e))
+                out.update(failed_at=i, secs=time.monotonic() - t0, code=e.code, text=str(e),
+                           released_before=released.is_set())
+                assert released.wait(timeout=30)  # the session lets go: the same call again
+                continue
+            i += 1
+            got.update(q.poll())
+    finally:
+        t.join(timeout=60)
+    while q.pending:
+        got.update(q.poll(wait=True))
+out["errors"] = errors
+out["got"] = sorted(got.items())
+print(json.dumps(out))
+"""
+
+
+def test_wait_bound_names_the_held_buffer(pkg, dev):
+    """When the bounded wait (SHA1CHUNK_VQ_WAIT_S, read once per process: a
+    child with a 1 s bound) runs out on another thread's polled, unreleased
+    head buffer -- the session here keeps it for 3 s -- the blocked submit
+    fails with ENOMEM and says whose the room is, not EHIP "drain not
+    progressing": the drain is fine.  After the release the same submit
+    succeeds and every verdict is right."""
+    env = dict(os.environ, SHA1CHUNK_VQ_MODE="persistent", SHA1CHUNK_VQ_RING_MIB="8", SHA1CHUNK_VQ_WAIT_S="1")
+    r = subprocess.run([sys.executable, "-c", _WAIT_BOUND_CHILD, ROOT], capture_output=True, text=True, env=env,
+                       cwd=ROOT, timeout=120)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    print({k: v for k, v in out.items() if k != "got"})
+    assert not out["errors"], out["errors"]
+    assert out["failed_at"] == 127  # the ring's 128th buffer
+    assert 0.9 <= out["secs"] <= 2.5, out["secs"]
+    assert not out["released_before"]
+    assert out["code"] == pkg.sha1chunk.ENOMEM and "polled and not released" in out["text"], (out["code"], out["text"])
+    assert "drain not progressing" not in out["text"]
+    want = {i: (0 if i % 7 else 1) for i in range(3 * 128)}
+    want[10**6] = 0
+    assert {int(k): v for k, v in out["got"]} == want
 
 
 def test_queue_create_destroy_beside_a_busy_queue(pkg, dev, corpus, monkeypatch):

@@ -247,6 +247,34 @@ int main() {
             });
         for (size_t i = 0; i < where.size(); ++i) bad += by_helper[i] && where[i] != first;
     }
+    // a pool made without a CPU set by a thread pinned to one CPU: its helpers
+    // are named s1pool and run on the process's CPUs, not on the creator's one
+    {
+        cpu_set_t proc;
+        bad += !s1host::process_cpus(&proc);
+        std::thread([&] {
+            cpu_set_t one;
+            CPU_ZERO(&one);
+            int first = -1;
+            for (int c = 0; c < CPU_SETSIZE && first < 0; ++c)
+                if (CPU_ISSET(c, &proc)) first = c;
+            CPU_SET(first, &one);
+            bad += pthread_setaffinity_np(pthread_self(), sizeof one, &one) != 0;
+            PartPool pool(3);
+            const pthread_t me = pthread_self();
+            std::vector<char> ok(4096, 1);
+            for (int job = 0; job < 20; ++job)
+                pool.run(ok.size(), [&](size_t i) {
+                    if (pthread_equal(pthread_self(), me)) return;
+                    cpu_set_t mine;
+                    char name[32] = {0};
+                    sched_getaffinity(0, sizeof mine, &mine);
+                    pthread_getname_np(pthread_self(), name, sizeof name);
+                    ok[i] = CPU_EQUAL(&mine, &proc) && std::string(name) == "s1pool";
+                });
+            for (char v : ok) bad += !v;
+        }).join();
+    }
     std::printf("pool %s\n", bad ? "BAD" : "ok");
     return bad ? 1 : 0;
 }
