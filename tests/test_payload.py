@@ -25,6 +25,8 @@ NEEDED = [
     "oracle/_ref/libsharef.so",
     "oracle/_ref/dropin/make-chunks",
     "oracle/_ref/dropin/verify_driver",
+    "oracle/_ref/dropin/reassembly_driver",
+    "oracle/_ref/reassembly_ref",
     "tests/golden/golden.json",
     "tests/golden/synth_4096x512k.bin",
     "tests/golden/C.tar.gz",
