@@ -15,6 +15,7 @@
 #include <unistd.h>
 #include <vector>
 
+#include "par_read.hpp"
 #include "sha1_runtime_internal.h"
 
 using namespace s1rt;
@@ -55,10 +56,8 @@ size_t stream_piece_bytes() {
     return b;
 }
 
-// size_hint: bytes the reader will deliver, when known (regular files);
-// small inputs then get a slot just big enough (the pinned allocation is a
-// one-process cost the make-chunks CLI pays on every run), mid-size inputs
-// are spread over all slots so reads and copies overlap.
+// size_hint: bytes the reader will deliver, when known (regular files); it
+// sizes the slots (par_read.hpp slot_geometry).
 long hash_stream_sized(sha1chunk_reader_fn reader, void* reader_ctx, sha1chunk_sink_fn sink,
                        void* sink_ctx, uint64_t size_hint) {
     if (!reader) return fail(SHA1CHUNK_EINVAL, "null reader");
@@ -68,17 +67,9 @@ long hash_stream_sized(sha1chunk_reader_fn reader, void* reader_ctx, sha1chunk_s
     std::lock_guard<std::mutex> lk(D->mu);
     if ((rc = discard_in_flight(*D))) return rc;
     const int nslots = stream_slots();
-    size_t slot_bytes = stream_slot_bytes();
-    bool one_fill = false;  // a known size that fits one slot: slot 0 alone, copies on its stream
-    if (size_hint) {
-        const size_t L = SHA1CHUNK_CHUNK_LEN;
-        const size_t whole = round_up(size_hint, L);
-        const size_t spread = std::max(size_t(64) << 20, round_up(size_hint / nslots, L));
-        slot_bytes = std::min({slot_bytes, whole, spread});
-        one_fill = whole <= slot_bytes;
-    }
-    const size_t per_slot = slot_bytes / SHA1CHUNK_CHUNK_LEN;  // 1024 chunks per 512 MiB
-    const size_t meta = round_up(per_slot * 12, kAlign);
+    const s1file::SlotGeometry geo = s1file::slot_geometry(size_hint, nslots, stream_slot_bytes());
+    const size_t slot_bytes = geo.slot_bytes, per_slot = geo.per_slot, meta = geo.meta;
+    bool one_fill = geo.one_fill;
     size_t next = 0;  // index of the next slot's first chunk
     size_t pend_first[kMaxSlots] = {}, pend_m[kMaxSlots] = {};
     auto finish = [&](int w) -> int {
@@ -171,52 +162,19 @@ static size_t fd_reader(void* ctx, void* dst, size_t n) {
         if (errno != EINTR) return (size_t)-1;
     }
 }
-// Regular files: each slot is filled by several threads with pread -- one
-// thread copies from the page cache at only ~5-10 GB/s, well under the PCIe
-// rate the pipeline can take.  The fd offset is left at the end of what was
-// read, as a read() loop would leave it.
-struct ParFile {
-    int fd;
-    off_t pos, end;
-    PartPool* pool;
-};
-static size_t par_reader(void* ctx, void* dst, size_t n) {
-    ParFile* f = static_cast<ParFile*>(ctx);
-    if (f->pos >= f->end) return 0;
-    const size_t want = std::min<size_t>(n, static_cast<size_t>(f->end - f->pos));
-    const size_t min_piece = size_t(8) << 20;
-    const int T = static_cast<int>(std::max<size_t>(1, std::min<size_t>(f->pool->width(), want / min_piece)));
-    const size_t piece = (want + T - 1) / T;
-    std::vector<size_t> got(T, 0);
-    std::atomic<bool> bad{false};
-    auto work = [&](int t) {
-        const size_t lo = std::min(want, piece * t), len = std::min(want, lo + piece) - lo;
-        uint8_t* d = static_cast<uint8_t*>(dst) + lo;
-        while (got[t] < len) {
-            const ssize_t r = pread(f->fd, d + got[t], len - got[t], f->pos + lo + got[t]);
-            if (r < 0) {
-                if (errno == EINTR) continue;
-                bad = true;
-                return;
-            }
-            if (r == 0) return;  // the file shrank under us
-            got[t] += static_cast<size_t>(r);
-        }
-    };
-    f->pool->run(static_cast<size_t>(T), [&](size_t t) { work(static_cast<int>(t)); });
-    if (bad) return (size_t)-1;
-    // bytes read contiguously from pos (a short piece ends the file)
-    size_t total = 0;
-    for (int t = 0; t < T; ++t) {
-        const size_t lo = std::min(want, piece * t), len = std::min(want, lo + piece) - lo;
-        total += got[t];
-        if (got[t] < len) {
-            f->end = f->pos + static_cast<off_t>(total);
-            break;
-        }
+// Regular files: ParFile and par_reader (par_read.hpp), whose counters are
+// added up over the process for s1be_file_read_stats.
+using s1file::ParFile;
+static_assert(s1file::kMetaAlign == kAlign, "par_read.hpp lays the slot's metadata out on the device's lines");
+constexpr sha1chunk_reader_fn par_reader = s1file::par_reader<>;
+std::atomic<uint64_t> g_read_calls{0}, g_read_split{0}, g_read_max_parts{0}, g_read_short{0};
+static void count_reads(const ParFile& f) {
+    g_read_calls += f.calls;
+    g_read_split += f.split_calls;
+    g_read_short += f.short_parts;
+    uint64_t seen = g_read_max_parts.load();
+    while (seen < f.max_parts && !g_read_max_parts.compare_exchange_weak(seen, f.max_parts)) {
     }
-    f->pos += static_cast<off_t>(total);
-    return total;
 }
 static void fd_sink(void* ctx, size_t first, const uint8_t* dig, size_t count) {
     FdSink* s = static_cast<FdSink*>(ctx);
@@ -243,8 +201,7 @@ int file_devices(uint64_t bytes) {
 long hash_file_devices(int fd, off_t pos, off_t end, int nd, int read_threads, FdSink* sk) {
     const uint64_t L = SHA1CHUNK_CHUNK_LEN;
     const uint64_t chunks = (static_cast<uint64_t>(end - pos) + L - 1) / L;
-    std::vector<long> got(nd, 0);
-    std::vector<off_t> stop(nd, 0);
+    std::vector<s1file::DevRange> rg(nd);
     std::vector<std::string> errs(nd);
     std::vector<std::thread> th;
     const int caller_dev = t_dev;
@@ -264,25 +221,18 @@ long hash_file_devices(int fd, off_t pos, off_t end, int nd, int read_threads, F
                 Shift* z = static_cast<Shift*>(ctx);
                 fd_sink(z->sk, z->c0 + first, dig, count);
             };
-            got[g] = hash_stream_sized(par_reader, &f, sink, &sh, static_cast<uint64_t>(b - a));
-            stop[g] = f.pos;
-            if (got[g] < 0) errs[g] = s1be_last_error();
+            const long got = hash_stream_sized(par_reader, &f, sink, &sh, static_cast<uint64_t>(b - a));
+            rg[g] = s1file::DevRange{got, c0, c1, b, f.pos};
+            count_reads(f);
+            if (got < 0) errs[g] = s1be_last_error();
         });
     }
     for (auto& t : th) t.join();
-    long n = 0;
-    for (int g = 0; g < nd; ++g) {
-        if (got[g] < 0) return fail(static_cast<int>(got[g]), "device %d: %s", g, errs[g].c_str());
-        const uint64_t c0 = chunks * g / nd, c1 = chunks * (g + 1) / nd;
-        n += got[g];
-        // a range that came up short (the file shrank) ends the file there
-        if (static_cast<uint64_t>(got[g]) < c1 - c0) {
-            (void)lseek(fd, stop[g], SEEK_SET);
-            return n;
-        }
-    }
-    (void)lseek(fd, stop[nd - 1], SEEK_SET);
-    return n;
+    // a range that came up short (the file shrank) ends the file there
+    const s1file::FileReduce red = s1file::reduce_ranges(rg.data(), nd);
+    if (red.bad >= 0) return fail(static_cast<int>(red.n), "device %d: %s", red.bad, errs[red.bad].c_str());
+    (void)lseek(fd, red.pos, SEEK_SET);
+    return red.n;
 }
 }  // namespace
 
@@ -309,6 +259,7 @@ long s1be_hash_fd(int fd, uint8_t* digests, size_t max_chunks, size_t* total_chu
             PartPool pool(read_threads - 1, near_cpus(g_dev[t_dev].id));
             ParFile f{fd, pos, end, &pool};
             n = hash_stream_sized(par_reader, &f, fd_sink, &sk, static_cast<uint64_t>(f.end - f.pos));
+            count_reads(f);
             (void)lseek(fd, f.pos, SEEK_SET);
         }
     } else {
@@ -317,6 +268,18 @@ long s1be_hash_fd(int fd, uint8_t* digests, size_t max_chunks, size_t* total_chu
     if (n < 0) return n;
     if (total_chunks) *total_chunks = static_cast<size_t>(n);
     return static_cast<long>(std::min(static_cast<size_t>(n), max_chunks));
+}
+
+// Diagnostics (tests/test_gpu_file_geometry.py; no front-end symbol): what the
+// process's par_reader calls did so far -- out[0] calls, out[1] calls split
+// over more than one part, out[2] the largest part count, out[3] parts that
+// came up short; reset != 0 then zeroes them.
+void s1be_file_read_stats(uint64_t out[4], int reset) {
+    std::atomic<uint64_t>* const c[4] = {&g_read_calls, &g_read_split, &g_read_max_parts, &g_read_short};
+    for (int i = 0; i < 4; ++i) {
+        if (out) out[i] = c[i]->load();
+        if (reset) c[i]->store(0);
+    }
 }
 
 }  // extern "C"
