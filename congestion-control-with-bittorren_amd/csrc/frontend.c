@@ -104,6 +104,15 @@ static int fail(int code, const char *fmt, ...) {
     X(int, update_batch, (void *, size_t, const uint32_t *, const void *, const uint64_t *,       \
                           const uint32_t *, size_t, unsigned))                                    \
     X(int, final_batch, (void *, size_t, const uint32_t *, size_t, uint8_t *, unsigned))          \
+    X(void *, pinned_alloc, (size_t))                                                             \
+    X(int, pinned_free, (void *))                                                                 \
+    X(int, gather_device_async, (const void *, const uint64_t *, const uint32_t *, size_t,        \
+                                 const uint32_t *, size_t, void *, const uint64_t *, uint64_t,    \
+                                 uint32_t *, void *))                                             \
+    X(int, hash_gather_batch, (const void *, const uint64_t *, const uint32_t *, size_t,          \
+                               const uint32_t *, size_t, uint8_t *, unsigned))                    \
+    X(int, verify_gather_batch, (const void *, const uint64_t *, const uint32_t *, size_t,        \
+                                 const uint32_t *, size_t, const uint8_t *, uint8_t *, unsigned)) \
     X(int, device_count, (void))                                                                  \
     X(int, set_device, (int))                                                                     \
     X(int, device_pci_bus_id, (int, char *, size_t))                                              \
@@ -926,4 +935,78 @@ FE_API int sha1chunk_final_batch(void *contexts, size_t n_contexts, const uint32
         return fail(SHA1CHUNK_EALIGN, "digest buffer must be 4-byte aligned");
     if (!(flags & SHA1CHUNK_DEVICE) && (rc = check_context_list(n_contexts, index, n))) return rc;
     FORWARD(int, final_batch(contexts, n_contexts, index, n, digests, flags));
+}
+
+/* ------------------------------------------ messages given as segment lists -- */
+/* Always on the gfx950 kernels, like the update batch.  The refusals that need
+ * no device are made here, before the backend is loaded (include/sha1chunk.h,
+ * "Contract of the host-array forms"). */
+FE_API void *sha1chunk_pinned_alloc(size_t bytes) {
+    if (bytes == 0) {
+        fail(SHA1CHUNK_EINVAL, "pinned allocation of 0 bytes");
+        return NULL;
+    }
+    if (backend_dev()) return NULL;
+    void *p = BE.pinned_alloc(bytes);
+    if (!p) fail(SHA1CHUNK_ENOMEM, "%s", BE.last_error());
+    return p;
+}
+
+FE_API int sha1chunk_pinned_free(void *p) {
+    if (!p) return SHA1CHUNK_OK;
+    FORWARD(int, pinned_free(p));
+}
+
+FE_API int sha1chunk_gather_device_async(const void *d_base, const uint64_t *d_seg_offsets,
+                                         const uint32_t *d_seg_lengths, size_t n_segments,
+                                         const uint32_t *d_seg_first, size_t n, void *d_dst,
+                                         const uint64_t *d_dst_offsets, uint64_t dst_bytes, uint32_t *d_out_lengths,
+                                         void *stream) {
+    if (n == 0) return SHA1CHUNK_OK;
+    if (n > BATCH_MAX || n_segments > BATCH_MAX) return fail(SHA1CHUNK_EINVAL, "n too large");
+    if (!d_base || !d_seg_first || !d_dst || !d_dst_offsets || (n_segments && (!d_seg_offsets || !d_seg_lengths)))
+        return fail(SHA1CHUNK_EINVAL, "null device pointer");
+    FORWARD(int, gather_device_async(d_base, d_seg_offsets, d_seg_lengths, n_segments, d_seg_first, n, d_dst,
+                                     d_dst_offsets, dst_bytes, d_out_lengths, stream));
+}
+
+/* The host forms' segment list: every message's range inside the list and its
+ * length at most 2^32 - 2 (the conditions the device form skips a message for;
+ * the stage is the library's own, so no destination can be too small). */
+static int check_segment_list(const void *base, const uint64_t *seg_offsets, const uint32_t *seg_lengths,
+                              size_t n_segments, const uint32_t *seg_first, size_t n, unsigned flags) {
+    if (n > BATCH_MAX || n_segments > BATCH_MAX) return fail(SHA1CHUNK_EINVAL, "n too large");
+    if (!base || !seg_first || (n_segments && (!seg_offsets || !seg_lengths))) return fail(SHA1CHUNK_EINVAL, "null pointer");
+    int rc = check_batch_flags(flags);
+    if (rc) return rc;
+    for (size_t i = 0; i < n; ++i) {
+        if (seg_first[i] > seg_first[i + 1] || seg_first[i + 1] > n_segments)
+            return fail(SHA1CHUNK_EINVAL, "message %zu: segments %u..%u of %zu", i, seg_first[i], seg_first[i + 1],
+                        n_segments);
+        uint64_t total = 0;
+        for (size_t s = seg_first[i]; s < seg_first[i + 1]; ++s) total += seg_lengths[s];
+        if (total > 0xfffffffeull) return fail(SHA1CHUNK_EINVAL, "message %zu: longer than 2^32 - 2 bytes", i);
+    }
+    return SHA1CHUNK_OK;
+}
+
+FE_API int sha1chunk_hash_gather_batch(const void *base, const uint64_t *seg_offsets, const uint32_t *seg_lengths,
+                                       size_t n_segments, const uint32_t *seg_first, size_t n, uint8_t *digests,
+                                       unsigned flags) {
+    if (n == 0) return SHA1CHUNK_OK;
+    if (!digests) return fail(SHA1CHUNK_EINVAL, "null pointer");
+    int rc = check_segment_list(base, seg_offsets, seg_lengths, n_segments, seg_first, n, flags);
+    if (rc) return rc;
+    FORWARD(int, hash_gather_batch(base, seg_offsets, seg_lengths, n_segments, seg_first, n, digests, flags));
+}
+
+FE_API int sha1chunk_verify_gather_batch(const void *base, const uint64_t *seg_offsets, const uint32_t *seg_lengths,
+                                         size_t n_segments, const uint32_t *seg_first, size_t n,
+                                         const uint8_t *expected, uint8_t *mismatch, unsigned flags) {
+    if (n == 0) return SHA1CHUNK_OK;
+    if (!expected || !mismatch) return fail(SHA1CHUNK_EINVAL, "null pointer");
+    int rc = check_segment_list(base, seg_offsets, seg_lengths, n_segments, seg_first, n, flags);
+    if (rc) return rc;
+    FORWARD(int, verify_gather_batch(base, seg_offsets, seg_lengths, n_segments, seg_first, n, expected, mismatch,
+                                     flags));
 }

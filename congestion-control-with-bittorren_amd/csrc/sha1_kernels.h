@@ -152,6 +152,32 @@ hipError_t launch_update_pre(const UpdateArgs& U, hipStream_t st);
 hipError_t launch_update_post(const UpdateArgs& U, hipStream_t st);
 hipError_t launch_update_final(const UpdateArgs& U, hipStream_t st);
 
+// Reassembly of messages given as segment lists (sha1_gather.hip; host side in
+// rt_gather.hip).  Message i is segments seg_first[i] .. seg_first[i+1]-1,
+// segment s being seg_len[s] bytes at base + seg_off[s]; it is written
+// contiguously at dst + dst_off[i], or skipped (gather_map.hpp skip_range,
+// skip_total): then no byte is written and its length word is 0xFFFFFFFF.
+// n and n_segments are at most 2^32 - 1025.
+struct GatherArgs {
+    const uint8_t* base;
+    const uint64_t* seg_off;
+    const uint32_t* seg_len;
+    uint64_t n_segments;
+    const uint32_t* seg_first;  // n + 1 entries
+    uint32_t n;
+    uint8_t* dst;
+    const uint64_t* dst_off;
+    uint64_t dst_bytes;
+    uint32_t* out_len;  // n length words for the caller, or null
+    // scratch: each segment's position inside its message (n_segments
+    // entries) and each message's length word (n entries)
+    uint32_t* pos;
+    uint32_t* mlen;
+    uint32_t* skipped;  // one device counter: messages skipped, added up
+};
+hipError_t launch_gather_scan(const GatherArgs& G, hipStream_t st);
+hipError_t launch_gather_copy(const GatherArgs& G, hipStream_t st);
+
 // One workgroup of kSynthThreads per chunk.  A launch holds fewer than 2^32
 // work-items per dimension (the dispatch packet's grid size is a 32-bit count
 // of work-items), so one call fills at most kSynthMaxChunks chunks; a larger

@@ -156,6 +156,22 @@ int launch_mixed_checked(const BatchArgs& A, const uint32_t* sorted_len, const B
     }
     return SHA1CHUNK_OK;
 }
+
+// Host memory the device reads in place (hipHostMalloc'd or registered).
+bool host_pinned(const void* p) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return at.type == hipMemoryTypeHost;
+}
+
+// Width of a device's pack pool (Device::pack), the caller included.
+int pack_threads() {
+    const char* e = getenv("SHA1CHUNK_COPY_THREADS");
+    return e ? std::max(1, atoi(e)) : 8;
+}
 }  // namespace s1rt
 
 namespace {
@@ -178,23 +194,10 @@ size_t slot_bytes_for(uint64_t total) {
     return std::min(hi, std::max(lo, static_cast<size_t>(total / 4)));
 }
 
-bool host_pinned(const void* p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return at.type == hipMemoryTypeHost;
-}
-
 // Pack entries [j0, j1) of a slot from pageable caller memory into pinned
 // staging on the device's pack pool: one thread copies ~10 GB/s, well under
 // the PCIe rate.  The entries are split into pool-width runs of about equal
 // bytes.
-int pack_threads() {
-    const char* e = getenv("SHA1CHUNK_COPY_THREADS");
-    return e ? std::max(1, atoi(e)) : 8;
-}
 void pack_range(PartPool& pool, uint8_t* h, const uint64_t* hoff, const uint8_t* base,
                 const uint64_t* offsets, const uint32_t* lengths, const std::vector<uint32_t>& ids,
                 size_t j0, size_t j1, size_t bytes) {

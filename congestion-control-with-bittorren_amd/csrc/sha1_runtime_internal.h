@@ -1,6 +1,6 @@
 // sha1_runtime_internal.h -- the internal header of the backend's host side
 // (rt_device.hip, sha1_runtime.hip, rt_file.hip, vq.hip, vq_persistent.hip,
-// sha1_pv.hip, rt_update.hip): the thread's error text and device, the device table and its
+// sha1_pv.hip, rt_update.hip, rt_gather.hip): the thread's error text and device, the device table and its
 // pipeline slots, host CPU placement, kernel choice and checked launches, and
 // what the verify queues and the progressive verifier share.  All of it is
 // internal to libsha1chunk_hip.so: the library exports its s1be_* entry
@@ -152,6 +152,8 @@ int launch_checked(int kernel, const BatchArgs& A, hipStream_t st, int cus = 256
 bool use_mixed(size_t n, int cus);
 int launch_mixed_checked(const BatchArgs& A, const uint32_t* sorted_len, const BigFix* big, uint32_t* plan, int cus,
                          hipStream_t st);
+bool host_pinned(const void* p);
+int pack_threads();
 
 // ---- vq.hip: shared by both queue modes and the progressive verifier -------
 int vq_copy_helpers();

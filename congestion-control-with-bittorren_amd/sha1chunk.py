@@ -123,6 +123,12 @@ _SIGNATURES = [
     ("sha1chunk_final_device_async", C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
     ("sha1chunk_update_batch", C.c_int, [_vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, C.c_uint]),
     ("sha1chunk_final_batch", C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint]),
+    ("sha1chunk_pinned_alloc", C.c_void_p, [C.c_size_t]),
+    ("sha1chunk_pinned_free", C.c_int, [_vp]),
+    ("sha1chunk_gather_device_async", C.c_int,
+     [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, C.c_uint64, _vp, _vp]),
+    ("sha1chunk_hash_gather_batch", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint]),
+    ("sha1chunk_verify_gather_batch", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, C.c_uint]),
     ("sha1chunk_device_count", C.c_int, []),
     ("sha1chunk_set_device", C.c_int, [C.c_int]),
     ("sha1chunk_get_device", C.c_int, []),
@@ -681,6 +687,91 @@ def final_batch(contexts: np.ndarray, index=None) -> np.ndarray:
     out = np.zeros((n, DIGEST_LEN), np.uint8)
     _check(lib().sha1chunk_final_batch(contexts.ctypes.data, nc, _addr(idx), n, out.ctypes.data, HOST),
            "sha1chunk_final_batch")
+    return out
+
+
+# ---- messages given as segment lists (device gather) ----
+def pinned_alloc(nbytes: int) -> np.ndarray:
+    """sha1chunk_pinned_alloc: nbytes of pinned host memory the device reads in
+    place (a packet ring), as a uint8 numpy view.  The view does not own the
+    memory: hand it (or its address) to pinned_free when done, and use no view
+    of it afterwards."""
+    p = lib().sha1chunk_pinned_alloc(nbytes)
+    if not p:
+        raise Sha1ChunkError(ENOMEM, "sha1chunk_pinned_alloc", lib().sha1chunk_last_error().decode(errors="replace"))
+    return np.ctypeslib.as_array((C.c_uint8 * nbytes).from_address(p))
+
+
+def pinned_free(buf) -> None:
+    """sha1chunk_pinned_free of a pinned_alloc view (or its address)."""
+    _check(lib().sha1chunk_pinned_free(_addr(buf)), "sha1chunk_pinned_free")
+
+
+def segment_csr(messages) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The CSR segment list (seg_offsets uint64, seg_lengths uint32, seg_first
+    uint32 of n + 1 entries) of a list of per-message [(offset, length), ...]
+    lists.  A tuple of three arrays is taken as such a list already."""
+    if isinstance(messages, tuple) and len(messages) == 3 and all(isinstance(a, np.ndarray) for a in messages):
+        off, ln, first = messages
+        return (np.ascontiguousarray(off, np.uint64), np.ascontiguousarray(ln, np.uint32),
+                np.ascontiguousarray(first, np.uint32))
+    first = np.zeros(len(messages) + 1, np.uint32)
+    first[1:] = np.cumsum([len(m) for m in messages], dtype=np.uint64)
+    flat = np.array([seg for m in messages for seg in m], np.uint64).reshape(-1, 2)
+    return np.ascontiguousarray(flat[:, 0]), flat[:, 1].astype(np.uint32), first
+
+
+def gather_device(base, seg_offsets, seg_lengths, seg_first, dst, dst_offsets, out_lengths=None, n: int | None = None,
+                  n_segments: int | None = None, dst_bytes: int | None = None, stream=None) -> None:
+    """Enqueue sha1chunk_gather_device_async: message i, the concatenation of
+    segments seg_first[i] .. seg_first[i+1]-1 (segment s = seg_lengths[s] bytes
+    at base + seg_offsets[s]), is written at dst + dst_offsets[i].  Torch CUDA
+    tensors (offsets int64, lengths / seg_first / out_lengths int32); base may
+    also be a pinned_alloc view."""
+    n = seg_first.numel() - 1 if n is None else n
+    n_segments = seg_lengths.numel() if n_segments is None else n_segments
+    dst_bytes = dst.numel() * dst.element_size() if dst_bytes is None else dst_bytes
+    _check(lib().sha1chunk_gather_device_async(_addr(base), _addr(seg_offsets), _addr(seg_lengths), n_segments,
+                                               _addr(seg_first), n, _addr(dst), _addr(dst_offsets), dst_bytes,
+                                               _addr(out_lengths), _stream_ptr(stream)),
+           "sha1chunk_gather_device_async")
+
+
+def _gather_base(base) -> tuple[int, int, object]:
+    """(address, flags, keep-alive) of a gather source: a torch CUDA tensor is
+    device memory, anything else host memory (pinned or pageable)."""
+    if hasattr(base, "data_ptr"):
+        return base.data_ptr(), DEVICE if base.is_cuda else HOST, base
+    b = np.frombuffer(base, np.uint8) if isinstance(base, (bytes, bytearray)) else base
+    if not b.flags["C_CONTIGUOUS"]:
+        raise ValueError("gather source must be contiguous")
+    return b.ctypes.data, HOST, b
+
+
+def hash_gather(base, messages) -> np.ndarray:
+    """sha1chunk_hash_gather_batch -> (n, 20) uint8 digests.  messages: a list
+    of per-message [(offset, length), ...] lists (or segment_csr's tuple);
+    base: a torch CUDA tensor, a pinned_alloc view or any host array."""
+    off, ln, first = segment_csr(messages)
+    addr, flags, _keep = _gather_base(base)
+    out = np.zeros((first.size - 1, DIGEST_LEN), np.uint8)
+    _check(lib().sha1chunk_hash_gather_batch(addr, off.ctypes.data, ln.ctypes.data, ln.size, first.ctypes.data,
+                                             first.size - 1, out.ctypes.data, flags), "sha1chunk_hash_gather_batch")
+    return out
+
+
+def verify_gather(base, messages, expected) -> np.ndarray:
+    """sha1chunk_verify_gather_batch -> n mismatch bytes (verify_hash's 0 / 1)
+    against expected, (n, 20) uint8."""
+    off, ln, first = segment_csr(messages)
+    addr, flags, _keep = _gather_base(base)
+    exp = np.ascontiguousarray(expected, np.uint8).reshape(-1)
+    if exp.size != (first.size - 1) * DIGEST_LEN:
+        raise ValueError("expected must hold 20 bytes per message")
+    out = np.zeros(first.size - 1, np.uint8)
+    _check(lib().sha1chunk_verify_gather_batch(addr, off.ctypes.data, ln.ctypes.data, ln.size, first.ctypes.data,
+                                               first.size - 1, exp.ctypes.data, out.ctypes.data, flags),
+           "sha1chunk_verify_gather_batch")
     return out
 
 

@@ -497,6 +497,117 @@ int sha1chunk_update_batch(void *contexts, size_t n_contexts, const uint32_t *in
 int sha1chunk_final_batch(void *contexts, size_t n_contexts, const uint32_t *index, size_t n,
                           uint8_t *digests, unsigned flags);
 
+/* ---- Messages given as segment lists: reassembly on the device -------------
+ * Every entry point above takes a message as one contiguous run of bytes.  A
+ * chunk on the receive path is not one: 512 KiB arrive as 354 DATA packets
+ * (353 x 1484 B + 436 B, each a 16-byte header and its payload in a datagram
+ * of at most 1500 bytes) that land wherever the socket call put them, in
+ * arrival order, and the reference copies every payload to
+ * data + 1484 * (seq - 1) (reliable_udp.c:339-341).  These calls hash and
+ * verify N messages from where their pieces lie -- a packet ring in pinned
+ * memory needs no CPU payload copy -- and can hand back the reassembled bytes.
+ *
+ * Segment list (CSR), shared by all forms: segment s is seg_lengths[s] bytes
+ *   at base + seg_offsets[s]; message i (0 <= i < n) is the concatenation, in
+ *   order, of segments seg_first[i] .. seg_first[i+1]-1; seg_first has n + 1
+ *   entries.  Segments may have any length (0 included) and any byte
+ *   alignment, may overlap, and a segment's bytes may be listed again under
+ *   another index for another message.  A message's length is the sum of its
+ *   segments' lengths.
+ * Reads.  The device reads a segment through the aligned 4-byte words that
+ *   hold its bytes: the other bytes of the first and last such word may be
+ *   read too, and nothing beyond (the rule of the update kernels).
+ *
+ * Device form (sha1chunk_gather_device_async): all pointers are device
+ *   pointers; d_base may also be memory from sha1chunk_pinned_alloc.  Message
+ *   i is written contiguously at d_dst + d_dst_offsets[i] and
+ *   d_out_lengths[i] (the array may be NULL) receives its length.  Exactly the
+ *   message's bytes are written: whole aligned 16-byte words inside it as
+ *   vector stores, its first and last partial words byte by byte, so bytes
+ *   around and between messages stay intact.  Asynchronous on `stream`; the
+ *   call never waits for the device (the first call on a device allocates a
+ *   128-byte counter); scratch comes from the stream-ordered allocator.
+ * Skipped messages.  Message i is skipped -- no byte of d_dst written,
+ *   d_out_lengths[i] = 0xFFFFFFFF -- when seg_first[i] > seg_first[i+1], when
+ *   seg_first[i+1] > n_segments, when its length exceeds 2^32 - 2, or when
+ *   d_dst_offsets[i] + length > dst_bytes, the way the update kernels skip a
+ *   bad context index.  A message without bytes writes nothing and has length 0.
+ * UNDEFINED in the device form (the device cannot see it): destination ranges
+ *   of different messages that overlap; d_dst overlapping the sources or the
+ *   arrays; and segment index ranges of two messages that overlap (possible
+ *   only when seg_first decreases somewhere): their messages' bytes are
+ *   unspecified.  Even then no load leaves the listed segments' words and no
+ *   store leaves the destination ranges of the messages that are not skipped.
+ *
+ * Host-array forms (sha1chunk_hash_gather_batch, sha1chunk_verify_gather_batch):
+ *   synchronous; the three segment arrays, digests, expected and mismatch are
+ *   host arrays, and flags says where `base` lives: SHA1CHUNK_HOST (pageable
+ *   or pinned host memory) or SHA1CHUNK_DEVICE.  digests[20*i ..] = SHA-1 of
+ *   message i; mismatch[i] follows verify_hash (0 = match, 1 = mismatch).
+ * Argument checks (made before anything reaches a device, outputs untouched):
+ *   n == 0 is a successful no-op; null pointers with n > 0 (the segment arrays
+ *   may be null when n_segments == 0), n or n_segments above 2^32 - 1025,
+ *   SHA1CHUNK_ALL_DEVICES or unknown flags, a message whose segment range is
+ *   reversed or reaches past n_segments, and a message longer than 2^32 - 2
+ *   bytes are SHA1CHUNK_EINVAL (every condition the device form skips for;
+ *   the destination is the library's own).
+ * Routing.  Always on the gfx950 kernels; SHA1CHUNK_HOST_SMALL does not apply
+ *   and there is no CPU fallback: without a device or the backend the calls
+ *   return SHA1CHUNK_ENODEV.
+ * Paths.  The batch goes in sub-batches of whole messages whose packed size
+ *   (every message on a 128-byte line of a device stage) stays under
+ *   SHA1CHUNK_GATHER_STAGE_MIB (1..65536, read per call, default 4096: 4096 x 512 KiB is one
+ *   sub-batch; the default rests on no measurement); a sub-batch holds at
+ *   least one message, however long.  With `base` in device memory, or in
+ *   host memory the device reads in place (sha1chunk_pinned_alloc, or any
+ *   other memory HIP reports as pinned), each sub-batch's segment arrays go
+ *   up, the gather kernels (csrc/sha1_gather.hip) reassemble into the stage
+ *   -- reading pinned memory over PCIe -- the stage is hashed as
+ *   sha1chunk_hash_device_async hashes under SHA1CHUNK_KERNEL_AUTO
+ *   (SHA1CHUNK_FORCE_KERNEL and SHA1CHUNK_SPLIT_UNIT apply) and compared on
+ *   the device for verify, and only digests or flags come back.  With `base`
+ *   in pageable memory (the compatibility path) the library's pack threads
+ *   copy each sub-batch's segments contiguously into a pinned fill and
+ *   sha1chunk_hash_batch's host path takes it from there; no gather kernel
+ *   runs.  Sub-batches do not overlap: one is finished before the next is
+ *   staged.  One host-form call runs at a time per device.
+ *
+ * Measured on MI355X (tools/gather_bench.py, profiles/gather.jsonl, DESIGN.md
+ * section 6; 4096 x 512 KiB as 354 packets each in a permuted ring of
+ * 1500-byte slots, median (min-max) of seven repetitions in one run).
+ * Device-resident, HIP events: the gather alone 1.964 (1.957-1.991) ms, 1018
+ * GiB/s of message bytes; gather then hash 7.978 (7.975-7.990) ms against
+ * 6.019 (6.010-6.059) for sha1chunk_hash_uniform_async on the same bytes laid
+ * contiguously: 1.96 ms (33 %) over it.  From sha1chunk_pinned_alloc memory
+ * read in place: the gather 43.45 (43.43-43.51) ms, 46.0 GiB/s, beside 37.50
+ * (37.47-37.52) ms, 53.3 GiB/s, for hipMemcpyAsync H2D of the same bytes;
+ * sha1chunk_verify_gather_batch 51.03 (50.84-51.05) ms wall clock against
+ * 44.05 (44.03-44.08) for sha1chunk_verify_batch from pinned contiguous
+ * memory.  The pageable path: 88.9 (88.7-91.1) ms.  Not measured: several
+ * sub-batches, ragged messages and other segment sizes, messages of more than
+ * 2048 segments, several devices, these calls beside a busy verify queue. */
+
+/* Pinned host memory the device can read in place (a packet ring): NULL and
+ * sha1chunk_last_error() on failure, on bytes == 0 and without a device. */
+void *sha1chunk_pinned_alloc(size_t bytes);
+/* Frees it (NULL: a successful no-op).  No call may still be reading it. */
+int sha1chunk_pinned_free(void *p);
+
+int sha1chunk_gather_device_async(const void *d_base, const uint64_t *d_seg_offsets,
+                                  const uint32_t *d_seg_lengths, size_t n_segments,
+                                  const uint32_t *d_seg_first, size_t n, void *d_dst,
+                                  const uint64_t *d_dst_offsets, uint64_t dst_bytes,
+                                  uint32_t *d_out_lengths, void *stream);
+
+int sha1chunk_hash_gather_batch(const void *base, const uint64_t *seg_offsets,
+                                const uint32_t *seg_lengths, size_t n_segments,
+                                const uint32_t *seg_first, size_t n, uint8_t *digests,
+                                unsigned flags);
+int sha1chunk_verify_gather_batch(const void *base, const uint64_t *seg_offsets,
+                                  const uint32_t *seg_lengths, size_t n_segments,
+                                  const uint32_t *seg_first, size_t n, const uint8_t *expected,
+                                  uint8_t *mismatch, unsigned flags);
+
 /* Device management. */
 int sha1chunk_device_count(void);
 int sha1chunk_set_device(int device);
