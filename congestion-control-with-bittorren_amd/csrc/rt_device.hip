@@ -261,6 +261,15 @@ void drain_cus_give(int dev, int cus) {
     std::lock_guard<std::mutex> lk(g_dev[dev].drain_mu);
     g_dev[dev].drain_cus -= cus;
 }
+
+// CUs of the calling thread's device that its persistent drains hold now
+// (0 before the device table exists).  A kernel shape that needs every CU it
+// counts on free asks this (sha1_runtime.hip split_unit).
+int drain_cus_held() {
+    if (!g_dev || t_dev < 0 || t_dev >= g_count) return 0;
+    std::lock_guard<std::mutex> lk(g_dev[t_dev].drain_mu);
+    return g_dev[t_dev].drain_cus;
+}
 }  // namespace s1rt
 
 // ================================================================ C ABI ====

@@ -29,9 +29,12 @@ hipError_t launch_lane(const BatchArgs& A, hipStream_t st);
 hipError_t launch_fused(const BatchArgs& A, hipStream_t st);
 // Split-kernel shapes (sha1_kernels.hip launch_split): 1 (1-block units), 4
 // (4-block units, two producers: <= 1 group per CU), 11 (8-wave workgroup of
-// two pairs: <= 2 groups per CU).  The A/B library (`make ab`,
+// two pairs: <= 2 groups per CU), kSplitUnitQuad (4-block units, two
+// producers, a quad of lanes per chunk and 16 chunks per workgroup: <= 16
+// chunks per CU; sha1_split.hpp kVQuad).  The A/B library (`make ab`,
 // -DSHA1CHUNK_AB_VARIANTS) also builds the study's other shapes and variant
 // flags (2, 3, 8-10, 12, 13, 10*U+V, 500+V, 569, 577-585, 86, 87, 590).
+constexpr int kSplitUnitQuad = 416;
 bool split_unit_built(int unit_blocks);
 hipError_t launch_split(const BatchArgs& A, int unit_blocks, hipStream_t st);
 // The other shapes of the split-kernel study: weak stubs in the product

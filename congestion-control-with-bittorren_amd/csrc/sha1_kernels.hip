@@ -1214,7 +1214,9 @@ __attribute__((weak)) hipError_t launch_split_study(const BatchArgs&, int, hipSt
     return hipErrorInvalidValue;
 }
 
-bool split_unit_built(int u) { return u == 1 || u == 4 || u == 11 || split_unit_study_built(u); }
+bool split_unit_built(int u) {
+    return u == 1 || u == 4 || u == 11 || u == kSplitUnitQuad || split_unit_study_built(u);
+}
 
 hipError_t launch_split(const BatchArgs& A, int unit_blocks, hipStream_t st) {
     if (A.n == 0) return hipSuccess;
@@ -1241,6 +1243,9 @@ hipError_t launch_split(const BatchArgs& A, int unit_blocks, hipStream_t st) {
         else
             hipLaunchKernelGGL((sha1_split_kernel<2, 2, kSplit8V, 2>), dim3((groups + 1) / 2), dim3(512), 0,
                                st, A);
+        break;
+    case kSplitUnitQuad:  // <= 16 chunks per CU: a quad of lanes per chunk, 16 chunks per workgroup
+        hipLaunchKernelGGL((sha1_split_kernel<4, 1, kSplitQuadV, 2>), dim3((A.n + 15u) / 16u), dim3(256), 0, st, A);
         break;
     default: return launch_split_study(A, unit_blocks, st);
     }

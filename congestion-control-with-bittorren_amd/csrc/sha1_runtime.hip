@@ -31,13 +31,23 @@ namespace {
 // CU one 8-wave workgroup holding both, 2-block units, two producers per
 // consumer sharing a SIMD and each consumer alone on its own (case 11:
 // 10-11 % faster than two 2-wave workgroups, profiles/split_2prod_sweep_r01.json);
-// else 1-block units (40 KiB).  SHA1CHUNK_SPLIT_UNIT forces a shape for A/B
-// runs: 1, 4, 11 in the product library; the study's other shapes and
+// else 1-block units (40 KiB).  Up to 16 chunks per CU (4096 chunks on 256
+// CUs, BASELINE config 2, down to the one-chunk call) the quad shape: four
+// lanes per chunk and 16 chunks per workgroup, so the consumer fetches a
+// block's W+K with 5 LDS reads instead of 20 (sha1_split.hpp kVQuad).  That
+// shape spreads 4096 chunks over every CU, so it counts only the CUs that
+// no persistent verify-queue drain holds (a drain workgroup keeps its CU's
+// whole LDS; two quad workgroups doubling up on a free CU put both
+// consumers on one SIMD and run at half speed: 10.7 against 5.85 ms beside
+// busy drains); with fewer CUs free, the shapes below as before.
+// SHA1CHUNK_SPLIT_UNIT forces a shape for A/B
+// runs: 1, 4, 11, 416 in the product library; the study's other shapes and
 // variants only in the A/B library (`make ab`, sha1_kernels.h).  Forcing a
 // shape this library does not hold fails the call (SHA1CHUNK_EINVAL,
 // launch_checked) instead of timing some other kernel.
 int split_unit(size_t n, int cus) {
     if (const char* e = getenv("SHA1CHUNK_SPLIT_UNIT")) return atoi(e);
+    if ((n + 15) / 16 <= size_t(std::max(0, cus - drain_cus_held()))) return kSplitUnitQuad;
     const size_t groups = (n + 63) / 64;
     if (groups <= size_t(cus)) return 4;
     if (groups <= size_t(cus) * 2) return 11;

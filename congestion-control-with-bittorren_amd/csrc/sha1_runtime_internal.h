@@ -145,6 +145,7 @@ const cpu_set_t* near_cpus(int id);
 const std::vector<cpu_set_t>& receive_domains(int id);
 int drain_cus_take(Device* D);
 void drain_cus_give(int dev, int cus);
+int drain_cus_held();
 
 // ---- sha1_runtime.hip: kernel choice and checked launches ------------------
 int choose_kernel(int kernel, size_t n, int cus);

@@ -700,6 +700,274 @@ __device__ __forceinline__ void consume_all(const BatchArgs& A, const Entry& en,
     if (valid) emit(A, en.id, h);
 }
 
+// ---------------------------------------------------------- quad split ----
+// kVQuad: four lanes (a quad) own one chunk, so a workgroup serves 16 chunks
+// (lane l: chunk l >> 2 of the group) and a batch of n chunks spreads over
+// ceil(n / 16) CUs.  A wave's issue cost does not depend on how many lanes
+// are live, so the redundant rounds are free; what the layout buys is the
+// schedule hand-off: one ds_read_b128 brings the quad 16 of a block's 80
+// W+K words (lane j of the quad holds words 16 q + 4 j .. + 3 of read q), 5
+// reads per block instead of 20, and round t takes its word from register
+// 4 (t >> 4) + (t & 3) of lane (t >> 2) & 3 through a DPP quad_perm
+// broadcast folded into the VOP2 add (v_add_u32_dpp: no extra instruction).
+// Measured alone on a SIMD (tools/gen_quad_probe.py,
+// profiles/quad_consumer_probe.json): the DPP add issues at the 4-cycle
+// floor (4.016 cycles per instruction, as the plain VOP2 add), but every DPP
+// add issued between a ds_read and the next s_waitcnt lgkmcnt(0) costs ~5
+// cycles more, wherever the read's data lands and long after it has landed
+// (1877 cycles per block against 1753.5 for today's stream); with an
+// explicit lgkmcnt(0) four rounds after the burst the block takes 1698.5.
+// Hence kQuadWaitRound.
+//
+// Ring: a block slot is 16 chunks x 80 words = 5 KiB, [q][lane][4 words] with
+// q = 0..4, so each read and each write is one contiguous conflict-free KiB;
+// 2 slots of U = 4 blocks are 40 KiB.  Wave roles, barriers and the masked
+// commit are those of the 4-block-unit shape (consumer on wave 0, producers
+// on waves 1 and 3, each writing one stage of every unit).  Producers: one
+// 16-byte load per lane brings the quad a whole block (lane j: piece j), the
+// other three pieces come over DPP, every lane expands the whole schedule
+// (redundant, the producers have the slack) and writes only the four words
+// of each group of 16 that its ring position holds: 5 ds_write_b128 per
+// block instead of 20.
+constexpr int kVQuad = 8192 * 4;
+constexpr int kQuadBlockBytes = 5 * 1024;
+constexpr int kQuadWaitRound = 4;  // rounds between the read burst and its s_waitcnt lgkmcnt(0)
+constexpr int kSplitQuadV = kVWK | kVUnmask | kVSkipWave2 | kVCoop | kVQuad;
+
+// x of lane SEL of the caller's quad (DPP quad_perm:[SEL,SEL,SEL,SEL]).
+template <int SEL>
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, SEL * 0x55, 0xf, 0xf, true);
+}
+
+template <int T, int END>
+struct RoundsQ {
+    __device__ __forceinline__ static void run(uint32_t (&v)[5], const uint32_t (&W)[20]) {
+        if constexpr (T < END) {
+            round_step<T, true>(v, quad_bcast<(T >> 2) & 3>(W[4 * (T >> 4) + (T & 3)]));
+            RoundsQ<T + 1, END>::run(v, W);
+        }
+    }
+};
+
+__device__ __forceinline__ void quad_read_w(const uint8_t* slot, uint32_t (&W)[20]) {
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        const uint4 x = *reinterpret_cast<const uint4*>(slot + q * 1024);
+        W[4 * q + 0] = x.x;
+        W[4 * q + 1] = x.y;
+        W[4 * q + 2] = x.z;
+        W[4 * q + 3] = x.w;
+    }
+}
+
+template <int U, int J, int V, bool MASK>
+__device__ __forceinline__ void quad_consume_block(uint32_t k, uint32_t T, uint32_t (&h)[5],
+                                                   const uint32_t (&Wc)[20], uint32_t (&Wn)[20],
+                                                   const uint8_t* ring, int lane, uint64_t& bw) {
+    // slot of block k + 1: as consume_block
+    constexpr int jn = (J + 1) % U;
+    constexpr int slot_idx = (((J + 1) / U) & 1) * U + jn;
+    const uint8_t* slot = ring + slot_idx * kQuadBlockBytes + lane * 16;
+    uint32_t v[5] = {h[0], h[1], h[2], h[3], h[4]};
+    if constexpr (jn == 0) split_barrier_or_timed<V>(bw);
+    __builtin_amdgcn_sched_barrier(0);
+    quad_read_w(slot, Wn);
+    __builtin_amdgcn_sched_barrier(0);
+    RoundsQ<0, kQuadWaitRound>::run(v, Wc);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the DPP adds after it issue at full rate
+    __builtin_amdgcn_sched_barrier(0);
+    RoundsQ<kQuadWaitRound, 80>::run(v, Wc);
+    if constexpr (MASK) {
+        const bool live = k < T;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) h[i] = live ? h[i] + v[i] : h[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) h[i] += v[i];
+    }
+}
+
+template <int U, int J, int V, bool MASK>
+struct QuadConsumeUnits {
+    __device__ __forceinline__ static void run(uint32_t k0, uint32_t T, uint32_t (&h)[5], uint32_t (&Wa)[20],
+                                               uint32_t (&Wb)[20], const uint8_t* ring, int lane, uint64_t& bw) {
+        if constexpr (J < 2 * U) {
+            quad_consume_block<U, J, V, MASK>(k0 + J, T, h, Wa, Wb, ring, lane, bw);
+            QuadConsumeUnits<U, J + 1, V, MASK>::run(k0, T, h, Wb, Wa, ring, lane, bw);
+        }
+    }
+};
+
+// Producer: the 80-word schedule of one block; after every 16 words the
+// window holds words 16 q .. 16 q + 15, of which lane j of the quad ships
+// words 4 j .. 4 j + 3 (+ K of their rounds: K is constant over each group of
+// 4 rounds, kq[q] is this lane's).
+template <int T>
+struct QuadSchedWrite {
+    __device__ __forceinline__ static void run(uint32_t (&w)[16], uint8_t* slot, bool j1, bool j2,
+                                               const uint32_t (&kq)[5]) {
+        if constexpr (T < 80) {
+            if constexpr (T >= 16) sched_step<T>(w);
+            if constexpr ((T & 15) == 15) {
+                constexpr int q = T >> 4;
+                uint32_t o[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t lo = j1 ? w[4 + i] : w[i], hi = j1 ? w[12 + i] : w[8 + i];
+                    o[i] = (j2 ? hi : lo) + kq[q];
+                }
+                *reinterpret_cast<uint4*>(slot + q * 1024) = make_uint4(o[0], o[1], o[2], o[3]);
+            }
+            QuadSchedWrite<T + 1>::run(w, slot, j1, j2, kq);
+        }
+    }
+};
+
+// As produce_block with two producers and 4-block units: a producer ends the
+// unit with its barrier after its stage's odd block.
+template <int U>
+__device__ __forceinline__ void quad_produce_block(uint32_t k, uint32_t (&w)[16], uint8_t* ring, int lane,
+                                                   const uint32_t (&kq)[5]) {
+    const uint32_t m = k / U, j = k - m * U;
+    QuadSchedWrite<0>::run(w, ring + ((m & 1u) * U + j) * kQuadBlockBytes + lane * 16, (lane & 1) != 0,
+                           (lane & 2) != 0, kq);
+    if ((k & 1u) == 1u) split_barrier();
+}
+
+// A lane's piece (16 bytes) of the quad's block -> the block's 16 big-endian
+// words in every lane of the quad.
+__device__ __forceinline__ void quad_block_words(const uint32_t (&x)[4], uint32_t (&w)[16]) {
+    uint32_t y[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = bswap(x[i]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        w[i] = quad_bcast<0>(y[i]);
+        w[4 + i] = quad_bcast<1>(y[i]);
+        w[8 + i] = quad_bcast<2>(y[i]);
+        w[12 + i] = quad_bcast<3>(y[i]);
+    }
+}
+
+// Stage s (blocks 2s, 2s + 1) of the quad's chunk: this lane's 16 bytes of each.
+__device__ __forceinline__ void quad_load_stage(const u32x4u* src, uint32_t s, uint32_t (&x)[8]) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const u32x4u v = src[8u * s + 4u * b];
+        x[4 * b + 0] = v.x;
+        x[4 * b + 1] = v.y;
+        x[4 * b + 2] = v.z;
+        x[4 * b + 3] = v.w;
+    }
+}
+
+// Producer side of one bulk stage from `cur`, which is then refilled with
+// this producer's stage after next (s + 4).
+template <int U>
+__device__ __forceinline__ void quad_produce_stage(const u32x4u* src, uint32_t s, uint32_t S, uint32_t (&cur)[8],
+                                                   uint8_t* ring, int lane, const uint32_t (&kq)[5]) {
+    uint32_t x0[4] = {cur[0], cur[1], cur[2], cur[3]}, x1[4] = {cur[4], cur[5], cur[6], cur[7]};
+    if (s + 4 < S) quad_load_stage(src, s + 4, cur);
+    uint32_t w[16];
+    quad_block_words(x0, w);
+    quad_produce_block<U>(2 * s, w, ring, lane, kq);
+    quad_block_words(x1, w);
+    quad_produce_block<U>(2 * s + 1, w, ring, lane, kq);
+}
+
+template <int U, int V>
+__device__ __forceinline__ void quad_consume_all(const BatchArgs& A, const Entry& en, bool valid, uint32_t T,
+                                                 uint32_t units, const uint8_t* ring, int lane, uint32_t wg) {
+    uint32_t h[5];
+    load_init(A, en.id, h);
+    uint32_t Wa[20], Wb[20];
+    split_barrier();  // B_0
+    quad_read_w(ring + lane * 16, Wa);
+    const uint32_t Tmin = __builtin_amdgcn_readfirstlane(wave_min(valid ? T : 0xffffffffu));
+    const uint32_t full = min(Tmin, units * U) / (2 * U) * (2 * U);
+    uint32_t k = 0;
+    uint64_t bw = 0;
+    const uint64_t t0 = (V & kVProbe) ? __builtin_amdgcn_s_memtime() : 0;
+    for (; k < full; k += 2 * U) QuadConsumeUnits<U, 0, V, false>::run(k, T, h, Wa, Wb, ring, lane, bw);
+    for (; k < units * U; k += 2 * U) QuadConsumeUnits<U, 0, V, true>::run(k, T, h, Wa, Wb, ring, lane, bw);
+    if constexpr ((V & kVProbe) != 0) {
+        const uint64_t tot = __builtin_amdgcn_s_memtime() - t0;
+        if (lane == 0) {  // over the group's first digest row (uniform batches: id = position)
+            uint32_t* o = reinterpret_cast<uint32_t*>(A.dig + 20ull * (wg * 16u));
+            o[0] = (uint32_t)bw;
+            o[1] = (uint32_t)(bw >> 32);
+            o[2] = (uint32_t)tot;
+            o[3] = (uint32_t)(tot >> 32);
+            o[4] = units * U;
+        }
+        return;
+    }
+    // the quad's four lanes hold the same state: one of them writes it
+    if (valid && (lane & 3) == 0) emit(A, en.id, h);
+}
+
+// The body of one quad workgroup: chunks wg*16 .. wg*16 + 15 over 40 KiB of LDS.
+template <int U, int V, int NPROD>
+__device__ __forceinline__ void quad_split_body(const BatchArgs& A, uint8_t* ring, uint32_t wg) {
+    static_assert(U == 4 && NPROD == 2 && (V & kVSkipWave2) != 0 && (V & kVWK) != 0 && (V & kVUnmask) != 0,
+                  "quad shape: 4-block units, two producers on waves 1 and 3, W+K shipped");
+    int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (wave == 2) return;  // never joins a barrier: an ended wave is not waited for
+    const bool producer = wave != 0;
+    const uint32_t pidx = wave == 3 ? 1u : 0u;
+    const int lane = threadIdx.x & 63;
+    const uint32_t e = wg * 16u + ((uint32_t)lane >> 2);
+    const bool valid = e < A.n;
+    // a quad past the batch reads the group's first chunk (wg*16 < n for
+    // every launched workgroup; clamped all the same)
+    Entry en = fetch_entry(A, valid ? e : min(wg * 16u, A.n - 1u));
+    if (!valid) en.len = 0;
+    const uint32_t T = valid ? (A.out_state ? (en.len >> 6) : total_blocks(en.len)) : 0u;
+    const uint32_t Tmax = __builtin_amdgcn_readfirstlane(wave_max(T));
+    const uint32_t units = (Tmax + 2 * U - 1) / (2 * U) * 2;
+    if (!producer) {
+        quad_consume_all<U, V>(A, en, valid, T, units, ring, lane, wg);
+        return;
+    }
+    // this lane's K per group of 16 rounds: rounds 16 q + 4 (lane & 3) ..
+    uint32_t kq[5];
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        const uint32_t t = 16u * q + 4u * ((uint32_t)lane & 3u);
+        kq[q] = t < 20 ? K0 : t < 40 ? K1 : t < 60 ? K2 : K3;
+    }
+    // bulk: the stages every chunk of the group has; this producer's are
+    // s = pidx, pidx + 2, ..: two in flight in registers
+    const uint32_t S = bulk_stages(en, valid);
+    const u32x4u* src = reinterpret_cast<const u32x4u*>(en.p) + (lane & 3);
+    uint32_t C0[8], C1[8];
+    uint32_t s = pidx;
+    if (s < S) quad_load_stage(src, s, C0);
+    if (s + 2 < S) quad_load_stage(src, s + 2, C1);
+    for (; s + 2 < S; s += 4) {
+        quad_produce_stage<U>(src, s, S, C0, ring, lane, kq);
+        quad_produce_stage<U>(src, s + 2, S, C1, ring, lane, kq);
+    }
+    if (s < S) {
+        quad_produce_stage<U>(src, s, S, C0, ring, lane, kq);
+        s += 2;
+    }
+    // tail and padding stages (whole units: blocks past a lane's T are never
+    // committed by the consumer); every lane of a quad builds the same words
+    for (; 2 * s < units * U; s += 2) {
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const uint32_t k = 2 * s + half;
+            uint32_t w[16];
+            if (k < T) tail_block_words(en, k, w);
+            quad_produce_block<U>(k, w, ring, lane, kq);
+        }
+    }
+    split_barrier();  // matches the consumer's last (unused) read
+}
+
 // PAIRS consumer/producer pairs per workgroup: waves 0..PAIRS-1 consume,
 // waves PAIRS..2*PAIRS-1 produce, pair p = (wave p, wave p+PAIRS).  Waves of
 // a workgroup are dealt to the CU's SIMDs cyclically, so with PAIRS = 4 each
@@ -719,6 +987,11 @@ __device__ __forceinline__ void consume_all(const BatchArgs& A, const Entry& en,
 // to this shape.
 template <int U, int PAIRS, int V, int NPROD>
 __device__ __forceinline__ void split_body(const BatchArgs& A, uint8_t* lds, uint32_t wg) {
+    if constexpr ((V & kVQuad) != 0) {
+        static_assert(PAIRS == 1, "quad shape: one consumer per workgroup");
+        quad_split_body<U, V, NPROD>(A, lds, wg);
+        return;
+    }
     constexpr bool WK = (V & kVWK) != 0;
     static_assert(PAIRS * 2 * U * kWBlockBytes <= 160 * 1024, "LDS");
     // Two producers for 2-block units (each owning one block per unit) were
@@ -918,10 +1191,13 @@ __device__ __forceinline__ void split_body(const BatchArgs& A, uint8_t* lds, uin
 // The 8-wave two-pair shape (product case 11, the mixed kernel's mode 1).
 constexpr int kSplit8V = kVWK | kVUnmask | kVLayout8 | kVCross | kVCoop;
 
+template <int U, int PAIRS, int V>
+constexpr int kSplitLdsBytes = (V & kVQuad) ? 2 * U * kQuadBlockBytes : PAIRS * 2 * U * kWBlockBytes;
+
 template <int U, int PAIRS, int V = kSplitV<U>, int NPROD = 1>
 __global__ __launch_bounds__((kSplitThreads<PAIRS, V, NPROD>)) void sha1_split_kernel(
     BatchArgs A) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[PAIRS * 2 * U * kWBlockBytes];
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kSplitLdsBytes<U, PAIRS, V>];
     split_body<U, PAIRS, V, NPROD>(A, lds, blockIdx.x);
 }
 

@@ -33,6 +33,8 @@ KERNELS = {
     "split_u4_2prod": "_Z17sha1_split_kernelILi4ELi1ELi8269ELi2EEv9BatchArgs",
     # <= 2 groups per CU: 8-wave workgroup, 2-block units (split_unit case 11)
     "split_u2_8wave": "_Z17sha1_split_kernelILi2ELi2ELi8581ELi2EEv9BatchArgs",
+    # <= 16 chunks per CU: a quad of lanes per chunk (split_unit case 416)
+    "split_u4_quad": "_Z17sha1_split_kernelILi4ELi1ELi41029ELi2EEv9BatchArgs",
 }
 
 
@@ -81,6 +83,9 @@ def main():
             blocks = c["v_perm_b32"] / 16 if name == "fused" else c["v_alignbit_b32"] / 160
             if best is None or sum(c.values()) / blocks < sum(best[1].values()) / best[2]:
                 best = (lab, c, blocks)
+        if best is None:  # no loop label this parser recognises
+            res["kernels"][name] = {"symbol": sym, "loop": None}
+            continue
         lab, c, blocks = best
         per = {k: v / blocks for k, v in sorted(c.items(), key=lambda kv: -kv[1])}
         valu = {k: v for k, v in per.items() if k.startswith("v_")}
