@@ -72,12 +72,18 @@ __device__ __forceinline__ constexpr uint32_t round_k() {
 // (The fused kernel keeps the two v_add3_u32: forms with every sum as a VOP2
 // add were measured no faster, profiles/fused_roundsum_ab_r02.json; their
 // code left the source in round 4.)
-template <int T, bool WK = false>
+// CH3 = true: Ch as one v_bitop3_b32 through the builtin.  The quad consumer
+// needs every instruction of its rounds to be 8 bytes long (sha1_split.hpp,
+// kVQuad), and chf() does not promise that: in the first block of its
+// unrolled loop hipcc splits it into a 4-byte v_xor_b32 and a bitop3.
+template <int T, bool WK = false, bool CH3 = false>
 __device__ __forceinline__ void round_step(uint32_t (&v)[5], uint32_t wt) {
     constexpr int ia = (5 - (T % 5)) % 5;
     constexpr int ib = (ia + 1) % 5, ic = (ia + 2) % 5, id = (ia + 3) % 5, ie = (ia + 4) % 5;
     uint32_t f;
-    if constexpr (T < 20)
+    if constexpr (T < 20 && CH3)
+        f = __builtin_amdgcn_bitop3_b32(v[ib], v[ic], v[id], 0xCA);
+    else if constexpr (T < 20)
         f = chf(v[ib], v[ic], v[id]);
     else if constexpr (T < 40)
         f = xor3(v[ib], v[ic], v[id]);

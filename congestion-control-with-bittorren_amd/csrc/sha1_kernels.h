@@ -33,7 +33,9 @@ hipError_t launch_fused(const BatchArgs& A, hipStream_t st);
 // producers, a quad of lanes per chunk and 16 chunks per workgroup: <= 16
 // chunks per CU; sha1_split.hpp kVQuad).  The A/B library (`make ab`,
 // -DSHA1CHUNK_AB_VARIANTS) also builds the study's other shapes and variant
-// flags (2, 3, 8-10, 12, 13, 10*U+V, 500+V, 569, 577-585, 86, 87, 590).
+// flags (2, 3, 8-10, 12, 13, 10*U+V, 500+V, 569, 577-585, 86, 87, 590; 417:
+// the quad shape with the consumer's cycle probe; 816 / 817: the quad shape
+// with 8-block units, which lost to 4, profiles/quad_unit_probe.json).
 constexpr int kSplitUnitQuad = 416;
 bool split_unit_built(int unit_blocks);
 hipError_t launch_split(const BatchArgs& A, int unit_blocks, hipStream_t st);

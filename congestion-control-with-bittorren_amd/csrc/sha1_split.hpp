@@ -710,20 +710,28 @@ __device__ __forceinline__ void consume_all(const BatchArgs& A, const Entry& en,
 // reads per block instead of 20, and round t takes its word from register
 // 4 (t >> 4) + (t & 3) of lane (t >> 2) & 3 through a DPP quad_perm
 // broadcast folded into the VOP2 add (v_add_u32_dpp: no extra instruction).
-// Measured alone on a SIMD (tools/gen_quad_probe.py,
-// profiles/quad_consumer_probe.json): the DPP add issues at the 4-cycle
-// floor (4.016 cycles per instruction, as the plain VOP2 add), but every DPP
-// add issued between a ds_read and the next s_waitcnt lgkmcnt(0) costs ~5
-// cycles more, wherever the read's data lands and long after it has landed
-// (1877 cycles per block against 1753.5 for today's stream); with an
-// explicit lgkmcnt(0) four rounds after the burst the block takes 1698.5.
-// Hence kQuadWaitRound.
+// Measured alone on a SIMD (tools/gen_quad_probe.py, gen_quad_hoist_probe.py;
+// profiles/quad_consumer_probe.json, quad_hoist_probe.json): the DPP add
+// issues at the 4-cycle floor (4.016 cycles per instruction, as the plain
+// VOP2 add) when its 8-byte encoding starts at an 8-byte boundary, and takes
+// ~5 cycles more at an address that is 4 mod 8 (the round stream alone: 1646.5
+// cycles per block aligned, 2043 with every DPP add shifted by one s_nop).
+// The other 8-byte instructions of a round do not care.  Every 4-byte
+// instruction in the stream (an s_waitcnt, a VOP2 feed-forward add) flips the
+// parity of what follows, so the rounds are kept free of them: the burst's
+// lgkmcnt(0) comes after round 79 (the set is not read before the next block;
+// with the five 4-byte feed-forward adds that makes six) and quad_align() pads
+// to the boundary in front of round 0 where it still has to.  The
+// whole block then takes 1678.5 cycles, as with a plain VOP2 add (1679),
+// against 1698.5 with an s_waitcnt four rounds after the burst, which put
+// those four rounds' DPP adds at the other parity than the rest.
 //
 // Ring: a block slot is 16 chunks x 80 words = 5 KiB, [q][lane][4 words] with
 // q = 0..4, so each read and each write is one contiguous conflict-free KiB;
-// 2 slots of U = 4 blocks are 40 KiB.  Wave roles, barriers and the masked
-// commit are those of the 4-block-unit shape (consumer on wave 0, producers
-// on waves 1 and 3, each writing one stage of every unit).  Producers: one
+// 2 slots of U blocks are 40 KiB (U = 4) or 80 KiB (U = 8).  Wave roles,
+// barriers and the masked commit are those of the 4-block-unit shape (consumer
+// on wave 0, producers on waves 1 and 3, which take the stages of a unit in
+// turn and join its barrier after their last stage in it).  Producers: one
 // 16-byte load per lane brings the quad a whole block (lane j: piece j), the
 // other three pieces come over DPP, every lane expands the whole schedule
 // (redundant, the producers have the slack) and writes only the four words
@@ -731,7 +739,6 @@ __device__ __forceinline__ void consume_all(const BatchArgs& A, const Entry& en,
 // block instead of 20.
 constexpr int kVQuad = 8192 * 4;
 constexpr int kQuadBlockBytes = 5 * 1024;
-constexpr int kQuadWaitRound = 4;  // rounds between the read burst and its s_waitcnt lgkmcnt(0)
 constexpr int kSplitQuadV = kVWK | kVUnmask | kVSkipWave2 | kVCoop | kVQuad;
 
 // x of lane SEL of the caller's quad (DPP quad_perm:[SEL,SEL,SEL,SEL]).
@@ -740,11 +747,15 @@ __device__ __forceinline__ uint32_t quad_bcast(uint32_t x) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, SEL * 0x55, 0xf, 0xf, true);
 }
 
+// What follows starts at an 8-byte boundary (the assembler pads with one
+// s_nop where it has to): see the DPP add's address parity above.
+__device__ __forceinline__ void quad_align() { asm volatile(".p2align 3"); }
+
 template <int T, int END>
 struct RoundsQ {
     __device__ __forceinline__ static void run(uint32_t (&v)[5], const uint32_t (&W)[20]) {
         if constexpr (T < END) {
-            round_step<T, true>(v, quad_bcast<(T >> 2) & 3>(W[4 * (T >> 4) + (T & 3)]));
+            round_step<T, true, true>(v, quad_bcast<(T >> 2) & 3>(W[4 * (T >> 4) + (T & 3)]));
             RoundsQ<T + 1, END>::run(v, W);
         }
     }
@@ -774,11 +785,19 @@ __device__ __forceinline__ void quad_consume_block(uint32_t k, uint32_t T, uint3
     __builtin_amdgcn_sched_barrier(0);
     quad_read_w(slot, Wn);
     __builtin_amdgcn_sched_barrier(0);
-    RoundsQ<0, kQuadWaitRound>::run(v, Wc);
+    // 80 rounds of 8-byte instructions from an 8-byte boundary; the fences
+    // keep hipcc from moving a 4-byte instruction (a feed-forward add, a
+    // wait) in between them
+    quad_align();
     __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the DPP adds after it issue at full rate
+    RoundsQ<0, 80>::run(v, Wc);
     __builtin_amdgcn_sched_barrier(0);
-    RoundsQ<kQuadWaitRound, 80>::run(v, Wc);
+    // lgkmcnt(0): Wn has landed (80 rounds after its burst).  In front of the
+    // feed-forward, where it also separates round 79's v_add3 from the add
+    // that reads its result (hipcc otherwise puts an s_nop there, and with
+    // it an odd number of 4-byte instructions into the block).
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_sched_barrier(0);
     if constexpr (MASK) {
         const bool live = k < T;
 #pragma unroll
@@ -787,6 +806,7 @@ __device__ __forceinline__ void quad_consume_block(uint32_t k, uint32_t T, uint3
 #pragma unroll
         for (int i = 0; i < 5; ++i) h[i] += v[i];
     }
+    __builtin_amdgcn_sched_barrier(0);
 }
 
 template <int U, int J, int V, bool MASK>
@@ -825,15 +845,21 @@ struct QuadSchedWrite {
     }
 };
 
-// As produce_block with two producers and 4-block units: a producer ends the
-// unit with its barrier after its stage's odd block.
+// As produce_block with two producers: the producers take a unit's U / 2
+// stages in turn, and each ends the unit with its barrier after the odd
+// block of its last stage in it (one of the unit's last two stages; with
+// U = 4 that is every stage).  U = 8 is an A/B-only shape (tools/ab_kernels.hip
+// 816 / 817): it lost its gate to U = 4 by 39 cycles per block
+// (profiles/quad_unit_probe.json), the product never launches it and no
+// committed test runs it; it was checked against hashlib once, when that
+// record was made, and is kept so that the measurement can be repeated.
 template <int U>
 __device__ __forceinline__ void quad_produce_block(uint32_t k, uint32_t (&w)[16], uint8_t* ring, int lane,
                                                    const uint32_t (&kq)[5]) {
     const uint32_t m = k / U, j = k - m * U;
     QuadSchedWrite<0>::run(w, ring + ((m & 1u) * U + j) * kQuadBlockBytes + lane * 16, (lane & 1) != 0,
                            (lane & 2) != 0, kq);
-    if ((k & 1u) == 1u) split_barrier();
+    if ((k & 1u) == 1u && ((k >> 1) % (U / 2)) + 2 >= U / 2) split_barrier();
 }
 
 // A lane's piece (16 bytes) of the quad's block -> the block's 16 big-endian
@@ -885,6 +911,10 @@ __device__ __forceinline__ void quad_consume_all(const BatchArgs& A, const Entry
     uint32_t Wa[20], Wb[20];
     split_barrier();  // B_0
     quad_read_w(ring + lane * 16, Wa);
+    // waited for here (and the initial state's loads), so that hipcc puts no
+    // s_waitcnt of its own in front of their first use in the loop, in between
+    // the aligned rounds
+    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0)
     const uint32_t Tmin = __builtin_amdgcn_readfirstlane(wave_min(valid ? T : 0xffffffffu));
     const uint32_t full = min(Tmin, units * U) / (2 * U) * (2 * U);
     uint32_t k = 0;
@@ -908,11 +938,12 @@ __device__ __forceinline__ void quad_consume_all(const BatchArgs& A, const Entry
     if (valid && (lane & 3) == 0) emit(A, en.id, h);
 }
 
-// The body of one quad workgroup: chunks wg*16 .. wg*16 + 15 over 40 KiB of LDS.
+// The body of one quad workgroup: chunks wg*16 .. wg*16 + 15 over 2 U x 5 KiB of LDS.
 template <int U, int V, int NPROD>
 __device__ __forceinline__ void quad_split_body(const BatchArgs& A, uint8_t* ring, uint32_t wg) {
-    static_assert(U == 4 && NPROD == 2 && (V & kVSkipWave2) != 0 && (V & kVWK) != 0 && (V & kVUnmask) != 0,
-                  "quad shape: 4-block units, two producers on waves 1 and 3, W+K shipped");
+    static_assert((U == 4 || U == 8) && NPROD == 2 && (V & kVSkipWave2) != 0 && (V & kVWK) != 0 &&
+                      (V & kVUnmask) != 0,
+                  "quad shape: 4- or 8-block units, two producers on waves 1 and 3, W+K shipped");
     int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave == 2) return;  // never joins a barrier: an ended wave is not waited for
     const bool producer = wave != 0;
@@ -993,11 +1024,11 @@ __device__ __forceinline__ void split_body(const BatchArgs& A, uint8_t* lds, uin
         return;
     }
     constexpr bool WK = (V & kVWK) != 0;
-    static_assert(PAIRS * 2 * U * kWBlockBytes <= 160 * 1024, "LDS");
+    static_assert((V & kVQuad) != 0 || PAIRS * 2 * U * kWBlockBytes <= 160 * 1024, "LDS");
     // Two producers for 2-block units (each owning one block per unit) were
     // measured slower at two groups per CU: 6 waves on 4 SIMDs put producers
     // on the consumers' SIMDs (profiles/split_2prod_sweep_r01.json).
-    static_assert(NPROD == 1 || (PAIRS == 1 && (U == 2 * NPROD || U == NPROD)) ||
+    static_assert((V & kVQuad) != 0 || NPROD == 1 || (PAIRS == 1 && (U == 2 * NPROD || U == NPROD)) ||
                       (PAIRS == 2 && U == NPROD && (V & kVLayout8) != 0),
                   "two producers: one stage (U = 4) or one block (U = 2, 8-wave layout) each per unit");
     int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

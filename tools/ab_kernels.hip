@@ -13,7 +13,7 @@
 
 namespace {
 constexpr int kStudyUnits[] = {2, 3, 20, 21, 24, 30, 31, 34, 44, 45, 504, 505, 569, 577, 585,
-                               8, 9, 10, 12, 13, 16, 17, 86, 87, 91, 92, 93, 94, 95, 96, 97, 98, 99, 81, 82, 83, 84, 417};
+                               8, 9, 10, 12, 13, 16, 17, 86, 87, 91, 92, 93, 94, 95, 96, 97, 98, 99, 81, 82, 83, 84, 417, 816, 817};
 }
 
 bool split_unit_study_built(int u) {
@@ -92,6 +92,13 @@ hipError_t launch_split_study(const BatchArgs& A, int unit, hipStream_t st) {
         break;
     case 417:  // the quad shape (product case 416) with the consumer probe: row 16 w of workgroup w
         hipLaunchKernelGGL((sha1_split_kernel<4, 1, kSplitQuadV | kVProbe, 2>), dim3((A.n + 15u) / 16u), dim3(256), 0,
+                           st, A);
+        break;
+    case 816:  // the quad shape with 8-block units (80 KiB ring, one consumer barrier per 8 blocks)
+        hipLaunchKernelGGL((sha1_split_kernel<8, 1, kSplitQuadV, 2>), dim3((A.n + 15u) / 16u), dim3(256), 0, st, A);
+        break;
+    case 817:  // ... with the consumer probe
+        hipLaunchKernelGGL((sha1_split_kernel<8, 1, kSplitQuadV | kVProbe, 2>), dim3((A.n + 15u) / 16u), dim3(256), 0,
                            st, A);
         break;
     case 81:  // 10-read bursts at rounds 10/50 (first pair) and 30/70 (second)

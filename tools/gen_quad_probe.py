@@ -30,6 +30,10 @@ What they showed on MI355X (profiles/quad_consumer_probe.json; DESIGN.md
 section 5, fact 5): the DPP add alone issues like the VOP2 add, but between a
 ds_read and the next s_waitcnt lgkmcnt(0) each one costs ~5 cycles more, so
 the burst needs an explicit lgkmcnt(0) a few rounds after it (b5w4).
+That reading was wrong: what costs the 5 cycles is a DPP add at an address
+that is 4 mod 8, and the 4-byte s_waitcnt instructions of these variants move
+the adds behind them from one parity to the other
+(tools/gen_quad_hoist_probe.py, profiles/quad_hoist_probe.json).
 
 Each variant is launched REPS + 1 times (the first discarded); the probe
 prints min / median / max cycles per block, so the spread of repeated runs
@@ -143,8 +147,8 @@ def variants():
     return out
 
 
-def main():
-    parts = ['''// quad_probe.hip -- GENERATED by tools/gen_quad_probe.py (diagnostic only).
+def main(vs=None, out="quad_probe.hip"):
+    parts = ['''// GENERATED by tools/gen_quad_probe.py or a sibling generator (diagnostic only).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -153,7 +157,7 @@ def main():
 #define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { \\
     fprintf(stderr, "%s: %s\\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 ''']
-    vs = variants()
+    vs = vs or variants()
     for name, body, lds in vs:
         parts.append(kernel(name, body, lds))
     parts.append(f'''
@@ -182,9 +186,10 @@ int main() {{
     for name, body, _ in vs:
         nvalu = sum(1 for l in body if l.startswith("v_"))
         nread = sum(1 for l in body if l.startswith("ds_read"))
-        parts.append(f'    run("{name}", {name}, {len(body)}, {nvalu}, {nread});\n')
+        ninstr = sum(1 for l in body if not l.startswith("."))  # directives are not instructions
+        parts.append(f'    run("{name}", {name}, {ninstr}, {nvalu}, {nread});\n')
     parts.append("    return 0;\n}\n")
-    with open(os.path.join(HERE, "quad_probe.hip"), "w") as f:
+    with open(os.path.join(HERE, out), "w") as f:
         f.write("".join(parts))
 
 
