@@ -16,7 +16,7 @@
 // adds offer().first to the buffer's or the dummy line's address once, then
 // 64 x clamped_block per step: source_offset's sum); buffer_of, lds_byte and
 // read_byte state what the kernel's rotating buffer index, the hardware's
-// lane-linear LDS write and coop4_read (sha1_split.hpp) do, for the check.
+// lane-linear LDS write and coop4_read (sha1_lane.hpp) do, for the check.
 #pragma once
 
 #include <stdint.h>
@@ -44,7 +44,7 @@ constexpr uint32_t buffer_of(uint32_t k) { return k % kBufs; }
 // then 16 x lane (the hardware's rule, not the kernel's choice).
 constexpr uint32_t lds_instr_base(uint32_t i) { return kSlots * kPieceBytes * i; }
 constexpr uint32_t lds_byte(uint32_t lane, uint32_t i) { return lds_instr_base(i) + kPieceBytes * lane; }
-// Where coop4_read (sha1_split.hpp) expects piece q of slot c.
+// Where coop4_read (sha1_lane.hpp) expects piece q of slot c.
 constexpr uint32_t read_byte(uint32_t c, uint32_t q) { return c * kBlockBytes + ((q + (c >> 2)) & 3u) * kPieceBytes; }
 
 // What a slot offers its four loaders: where its first block lies -- a byte

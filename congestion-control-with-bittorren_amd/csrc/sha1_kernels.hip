@@ -47,6 +47,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "sha1_fused.hpp"
 #include "sha1_split.hpp"
 
 // The mixed planner's measured constants (us per block of a group of 64
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) void sha1_lane_kernel(BatchArgs A) {
 }
 
 // --------------------------------------------------------------- fused ----
-// (body: fused_body in sha1_split.hpp)
+// (body: fused_body in sha1_fused.hpp)
 __global__ __launch_bounds__(256) void sha1_fused_kernel(BatchArgs A) {
     fused_body(A, blockIdx.x * 256u + threadIdx.x);
 }
@@ -1218,15 +1219,21 @@ bool split_unit_built(int u) {
     return u == 1 || u == 4 || u == 11 || u == kSplitUnitQuad || split_unit_study_built(u);
 }
 
+// The product shapes' block sizes (launch_shape, sha1_split.hpp, takes them
+// from kSplitThreads): pinned, so that a change of the formula shows here.
+static_assert(kSplitThreads<1, kSplitV<1>, 1> == 128, "unit 1: consumer + producer");
+static_assert(kSplitThreads<1, kSplitV<4>, kSplitNProd<4>> == 256, "unit 4: consumer, two producers, wave 2 empty");
+static_assert(kSplitThreads<2, kSplit8V, 2> == 512 && kSplitThreads<2, kSplit8V & ~kVCoop, 2> == 512,
+              "unit 11: the 8-wave layout");
+static_assert(kSplitThreads<1, kSplitQuadV, 2> == 256, "unit 416: as unit 4");
+
 hipError_t launch_split(const BatchArgs& A, int unit_blocks, hipStream_t st) {
     if (A.n == 0) return hipSuccess;
     const uint32_t groups = (A.n + 63u) / 64u;
     switch (unit_blocks) {
-    case 1: hipLaunchKernelGGL((sha1_split_kernel<1, 1>), dim3(groups), dim3(128), 0, st, A); break;
+    case 1: launch_shape<1, 1>(A, groups, st); break;
     case 4:  // two producers per consumer (kSplitNProd<4>), wave 2 empty: 256 threads
-        hipLaunchKernelGGL((sha1_split_kernel<4, 1, kSplitV<4>, kSplitNProd<4>>), dim3(groups),
-                           dim3(64 * (1 + kSplitNProd<4>) + ((kSplitV<4> & kVSkipWave2) ? 64 : 0)), 0,
-                           st, A);
+        launch_shape<4, 1, kSplitV<4>, kSplitNProd<4>>(A, groups, st);
         break;
     case 11:  // <= 2 groups per CU: 2 pairs x (consumer + 2 producers), 2-block
               // units, 8-wave layout, producer SIMDs crossed between the pairs.
@@ -1238,14 +1245,12 @@ hipError_t launch_split(const BatchArgs& A, int unit_blocks, hipStream_t st) {
               // (profiles/shard_ab_r03.json).  Ragged (possibly scattered)
               // chunks keep the shared loads.
         if (A.off == nullptr && A.order == nullptr)
-            hipLaunchKernelGGL((sha1_split_kernel<2, 2, kSplit8V & ~kVCoop, 2>), dim3((groups + 1) / 2), dim3(512),
-                               0, st, A);
+            launch_shape<2, 2, kSplit8V & ~kVCoop, 2>(A, (groups + 1) / 2, st);
         else
-            hipLaunchKernelGGL((sha1_split_kernel<2, 2, kSplit8V, 2>), dim3((groups + 1) / 2), dim3(512), 0,
-                               st, A);
+            launch_shape<2, 2, kSplit8V, 2>(A, (groups + 1) / 2, st);
         break;
     case kSplitUnitQuad:  // <= 16 chunks per CU: a quad of lanes per chunk, 16 chunks per workgroup
-        hipLaunchKernelGGL((sha1_split_kernel<4, 1, kSplitQuadV, 2>), dim3((A.n + 15u) / 16u), dim3(256), 0, st, A);
+        launch_shape<4, 1, kSplitQuadV, 2>(A, (A.n + 15u) / 16u, st);
         break;
     default: return launch_split_study(A, unit_blocks, st);
     }

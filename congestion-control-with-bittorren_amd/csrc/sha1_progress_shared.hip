@@ -12,7 +12,7 @@
 // entry: instruction i reads the whole 64-byte block of entries 16i .. 16i+15
 // (pv_shared_map.hpp), so one instruction touches 16 sessions' full blocks.
 // The blocks go straight to LDS (LDS-DMA, global_load_lds_dwordx4; glds16 of
-// sha1_split.hpp) in coop4_store's swizzled image -- the swizzle is on the
+// sha1_fused.hpp) in coop4_store's swizzled image -- the swizzle is on the
 // source address -- five 4 KiB buffers, four block steps ahead (a PCIe round
 // trip is ~2 us each way, a block ~1.25 us of compression), and each lane
 // takes its own block back with coop4_read: the LDS-DMA loop of
@@ -43,7 +43,7 @@
 #include <stdint.h>
 
 #include "pv_shared_map.hpp"
-#include "sha1_split.hpp"
+#include "sha1_fused.hpp"
 
 namespace {
 

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Where a split consumer's time goes (round 5): runs the A/B library's probe
-shapes (SHA1CHUNK_SPLIT_UNIT 97 / 98 / 99: the 8-wave two-pair shape as the
-product launches it, the same with phase-shifted 10-read bursts, and the
-config-2 one-group shape), whose consumer waves time their s_barrier waits
+shapes (SHA1CHUNK_SPLIT_UNIT 97 / 99: the 8-wave two-pair shape as the
+product launches it and the config-2 one-group shape; round 5 also probed
+the 8-wave shape with phase-shifted 10-read bursts, whose code is in git
+history up to commit b770692), whose consumer waves time their s_barrier waits
 and their whole block loop with the shader clock and write the counts over
 their group's first digest row.  Prints per shape: kernel ms, mean loop
 cycles per block, mean barrier-wait cycles per block (the consumer waiting
@@ -24,7 +25,7 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", required=True)
-    ap.add_argument("--cases", default="97:32768,98:32768,99:4096")
+    ap.add_argument("--cases", default="97:32768,99:4096")
     ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
     import torch
