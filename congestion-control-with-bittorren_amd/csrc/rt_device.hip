@@ -4,6 +4,7 @@
 // CU budget of the persistent verify-queue drains.  Declared in
 // sha1_runtime_internal.h; the C entry points here are the device queries.
 #include <algorithm>
+#include <atomic>
 #include <cctype>
 #include <cstdarg>
 #include <cstdio>
@@ -19,6 +20,9 @@
 using namespace s1rt;
 
 namespace {
+// Kernel launches of this process by kind (count_launch, s1be_launch_stats).
+std::atomic<uint64_t> g_launches[kLaunchCounters];
+
 // First line of a sysfs file ("" if it cannot be read).
 std::string sysfs_line(const char* path) {
     char buf[4096] = {0};
@@ -317,4 +321,19 @@ int s1be_receive_cpus(int device, unsigned slot, void* mask, size_t len, unsigne
     return CPU_COUNT(&d);
 }
 
+// Diagnostics (tests/launch_stats.py; no front-end symbol): how often each
+// kind of kernel was enqueued in this process so far, out[0 .. 10] in
+// LaunchCounter's order (sha1_kernels.h); reset != 0 then zeroes them.
+// out[11]: the CUs the calling thread's device's persistent drains hold now
+// (drain_cus_held), a gauge that reset leaves alone.
+void s1be_launch_stats(uint64_t* out, int reset) {
+    for (int i = 0; i < kLaunchCounters; ++i) {
+        if (out) out[i] = g_launches[i].load(std::memory_order_relaxed);
+        if (reset) g_launches[i].store(0, std::memory_order_relaxed);
+    }
+    if (out) out[kLaunchCounters] = static_cast<uint64_t>(drain_cus_held());
+}
+
 }  // extern "C"
+
+void count_launch(LaunchCounter which) { g_launches[which].fetch_add(1, std::memory_order_relaxed); }

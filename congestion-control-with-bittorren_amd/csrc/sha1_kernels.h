@@ -25,6 +25,22 @@ struct BatchArgs {
     const uint32_t* plan;
 };
 
+// Launch counters (diagnostics: s1be_launch_stats, rt_device.hip; read by
+// tests/launch_stats.py).  One per distinct thing the library can launch,
+// process-wide, counted by the launcher where it enqueues the kernels (after
+// its n == 0 return), not where the shape is chosen.  The layout of
+// s1be_launch_stats' out[12] is this enum's order:
+//   [0] lane  [1] fused  [2] split unit 1  [3] split unit 4
+//   [4] split unit 11, lane-per-chunk loads  [5] split unit 11, shared loads
+//   [6] quad (unit 416)  [7] a study shape (A/B library)  [8] mixed
+//   [9] length sort  [10] persistent verify-queue drain
+//   [11] gauge, never reset: CUs the calling thread's device's drains hold
+enum LaunchCounter {
+    kLaunchLane, kLaunchFused, kLaunchSplit1, kLaunchSplit4, kLaunchSplit11Lane, kLaunchSplit11Shared,
+    kLaunchQuad, kLaunchStudy, kLaunchMixed, kLaunchSort, kLaunchDrain, kLaunchCounters
+};
+void count_launch(LaunchCounter which);
+
 hipError_t launch_lane(const BatchArgs& A, hipStream_t st);
 hipError_t launch_fused(const BatchArgs& A, hipStream_t st);
 // Split-kernel shapes (sha1_kernels.hip launch_split): 1 (1-block units), 4

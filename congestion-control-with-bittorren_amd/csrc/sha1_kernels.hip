@@ -1197,12 +1197,14 @@ __global__ __launch_bounds__(256) void compare_kernel(const uint8_t* dig, const 
 hipError_t launch_lane(const BatchArgs& A, hipStream_t st) {
     if (A.n == 0) return hipSuccess;
     const uint32_t grid = (A.n + 255u) / 256u;
+    count_launch(kLaunchLane);
     hipLaunchKernelGGL(sha1_lane_kernel, dim3(grid), dim3(256), 0, st, A);
     return hipGetLastError();
 }
 
 hipError_t launch_fused(const BatchArgs& A, hipStream_t st) {
     if (A.n == 0) return hipSuccess;
+    count_launch(kLaunchFused);
     hipLaunchKernelGGL(sha1_fused_kernel, dim3((A.n + 255u) / 256u), dim3(256), 0, st, A);
     return hipGetLastError();
 }
@@ -1231,8 +1233,12 @@ hipError_t launch_split(const BatchArgs& A, int unit_blocks, hipStream_t st) {
     if (A.n == 0) return hipSuccess;
     const uint32_t groups = (A.n + 63u) / 64u;
     switch (unit_blocks) {
-    case 1: launch_shape<1, 1>(A, groups, st); break;
+    case 1:
+        count_launch(kLaunchSplit1);
+        launch_shape<1, 1>(A, groups, st);
+        break;
     case 4:  // two producers per consumer (kSplitNProd<4>), wave 2 empty: 256 threads
+        count_launch(kLaunchSplit4);
         launch_shape<4, 1, kSplitV<4>, kSplitNProd<4>>(A, groups, st);
         break;
     case 11:  // <= 2 groups per CU: 2 pairs x (consumer + 2 producers), 2-block
@@ -1244,12 +1250,16 @@ hipError_t launch_split(const BatchArgs& A, int unit_blocks, hipStream_t st) {
               // against 6.41 ms at 32768 chunks, steady clock
               // (profiles/shard_ab_r03.json).  Ragged (possibly scattered)
               // chunks keep the shared loads.
-        if (A.off == nullptr && A.order == nullptr)
+        if (A.off == nullptr && A.order == nullptr) {
+            count_launch(kLaunchSplit11Lane);
             launch_shape<2, 2, kSplit8V & ~kVCoop, 2>(A, (groups + 1) / 2, st);
-        else
+        } else {
+            count_launch(kLaunchSplit11Shared);
             launch_shape<2, 2, kSplit8V, 2>(A, (groups + 1) / 2, st);
+        }
         break;
     case kSplitUnitQuad:  // <= 16 chunks per CU: a quad of lanes per chunk, 16 chunks per workgroup
+        count_launch(kLaunchQuad);
         launch_shape<4, 1, kSplitQuadV, 2>(A, (A.n + 15u) / 16u, st);
         break;
     default: return launch_split_study(A, unit_blocks, st);
@@ -1288,6 +1298,7 @@ hipError_t launch_mixed(const BatchArgs& A, const uint32_t* sorted_len, const Bi
     uint64_t* lay_tb = reinterpret_cast<uint64_t*>(plan + 64);
     uint32_t* lay_bits = reinterpret_cast<uint32_t*>(lay_tb + words);
     const uint32_t* lay_blk = lay_bits + words;
+    count_launch(kLaunchMixed);
     if (!forced) {
         const hipError_t le = launch_plan_layout(A, sorted_len, big, plan, st);
         if (le != hipSuccess) return le;
@@ -1316,6 +1327,7 @@ hipError_t launch_mixed(const BatchArgs& A, const uint32_t* sorted_len, const Bi
 }
 
 hipError_t launch_vq_drain(const VqDrainArgs& Q, uint32_t grid, hipStream_t st) {
+    count_launch(kLaunchDrain);
     hipLaunchKernelGGL(sha1_vq_drain_kernel, dim3(grid), dim3(kMixedThreads), 0, st, Q);
     return hipGetLastError();
 }

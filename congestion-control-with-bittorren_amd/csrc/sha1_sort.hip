@@ -335,6 +335,7 @@ hipError_t sort_by_length_desc(const uint32_t* d_len, uint32_t n, const uint32_t
     uint32_t* big_cnt = big ? reinterpret_cast<uint32_t*>(bigm) : nullptr;
     uint32_t* big_len = big ? reinterpret_cast<uint32_t*>(bigm + align256(size_t(tiles) * sizeof(uint32_t))) : nullptr;
     uint32_t* big_id = big ? big_len + align256(kBigExact * sizeof(uint32_t)) / sizeof(uint32_t) : nullptr;
+    count_launch(kLaunchSort);
     hipLaunchKernelGGL(sort_hist<1>, dim3(tiles), dim3(kSortThreads), 0, st, d_len, (const uint16_t*)nullptr, keys,
                        hist1, n, big_cnt);
     if (scan) hipLaunchKernelGGL(hist_scan, dim3(256), dim3(kScanThreads), 0, st, hist1, tiles, pre1, tot1);

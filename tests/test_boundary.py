@@ -167,8 +167,9 @@ def test_front_end_links_libc_only(built):
     assert "s1be_hash_batch" in syms
     assert "s1be_sort_order_async" in syms  # diagnostics for tests/test_gpu_sort.py
     assert "s1be_file_read_stats" in syms  # diagnostics for tests/test_gpu_file_geometry.py
+    assert "s1be_launch_stats" in syms  # diagnostics for tests/launch_stats.py
     front = subprocess.run(["nm", "-D", "--defined-only", built], capture_output=True, text=True).stdout
-    assert "file_read_stats" not in front  # no front-end symbol
+    assert "file_read_stats" not in front and "launch_stats" not in front  # no front-end symbol
     # every defined dynamic symbol is an entry point (csrc/backend.map): no
     # launcher, kernel stub, class or template instantiation leaks out
     names = [line.split()[-1] for line in nm.splitlines() if line.strip()]

@@ -87,7 +87,7 @@ def _same(got, want, lens, off, what):
 
 
 @pytest.mark.parametrize("kernel,unit", [("lane", None), ("fused", None), ("split", "1"), ("split", "4"),
-                                         ("split", "11"), ("auto", None)])
+                                         ("split", "11"), ("split", "416"), ("auto", None)])
 def test_ragged_offsets_across_2_32(pkg, dev, wide, window, ragged, monkeypatch, kernel, unit):
     for k in ENV_KNOBS:
         monkeypatch.delenv(k, raising=False)

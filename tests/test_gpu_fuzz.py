@@ -12,7 +12,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 KERNELS = ["lane", "fused", "split", "auto"]
-SPLIT_UNITS = [1, 4, 11]  # the product library's split shapes
+SPLIT_UNITS = [1, 4, 11, 416]  # the product library's split shapes
 
 
 def _lengths(rng, n):
@@ -54,7 +54,8 @@ def test_random_batches_every_kernel(pkg, dev, oracle, seed, monkeypatch):
     d_host = torch.from_numpy(host).cuda()
     d_off = torch.from_numpy(off.astype(np.int64)).cuda()
     d_len = torch.from_numpy(lens.astype(np.int32)).cuda()
-    kernels = KERNELS + [f"split:{u}" for u in rng.choice(SPLIT_UNITS, 3, replace=False)]
+    # every split shape, in an order drawn after the batch (the seeds' batches stay as they were)
+    kernels = KERNELS + [f"split:{u}" for u in rng.permutation(SPLIT_UNITS)]
     for k in kernels:
         if k.startswith("split:"):
             monkeypatch.setenv("SHA1CHUNK_SPLIT_UNIT", k.split(":")[1])

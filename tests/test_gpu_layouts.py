@@ -56,11 +56,12 @@ def _check(got, want, what):
 
 
 @pytest.mark.parametrize("align", [16, 1])
-@pytest.mark.parametrize("unit", ["4", "11", "1"])
+@pytest.mark.parametrize("unit", ["4", "11", "1", "416"])
 def test_split_shapes_scattered(pkg, dev, oracle, monkeypatch, unit, align):
     """Equal-ish 9 KiB chunks (a few ragged tails) in a random order, three
-    and a half groups: the one-group (unit 4), 8-wave (unit 11) and 1-block
-    (unit 1, lane-per-chunk loads) split shapes."""
+    and a half groups: the one-group (unit 4), 8-wave (unit 11), 1-block
+    (unit 1, lane-per-chunk loads) and quad (unit 416, 16 chunks per
+    workgroup) split shapes."""
     torch = dev
     rng = np.random.default_rng(31 + int(unit))
     n = 64 * 3 + 37

@@ -951,11 +951,11 @@ def test_make_chunks_from_stream_position(pkg, dev, golden, fixture_files, tmp_p
     assert out == "".join(f"{i} {h}\n" for i, h in enumerate(exp)) + "eof 1\n"
 
 
-@pytest.mark.parametrize("unit", [1, 4, 11])
+@pytest.mark.parametrize("unit", [1, 4, 11, 416])
 def test_every_split_shape_ragged(pkg, dev, oracle, unit, monkeypatch):
     """Every split-kernel shape the product library builds (SHA1CHUNK_SPLIT_UNIT
     forces it: 1-block units, 4-block units with two producers, the 8-wave
-    two-pair layout) on ragged lengths with byte-misaligned starts, a partial
+    two-pair layout, the quad shape) on ragged lengths with byte-misaligned starts, a partial
     last workgroup and a lane-count that is not a multiple of 64: bit-exact
     vs the oracle.  (The round-1 study's other shapes live in the A/B build
     only, `make ab`.)"""

@@ -3,7 +3,8 @@ kVQuad: the read burst, 80 rounds with no wait between them, the burst's
 lgkmcnt(0) after round 79, then the feed-forward; the first W+K set and the
 initial state waited for in front of the loop), forced
 (SHA1CHUNK_SPLIT_UNIT=416) and through AUTO,
-bit-exact against hashlib.sha1.
+bit-exact against hashlib.sha1; that both calls ran the quad shape is read
+from the backend's launch counters (launch_stats.py).
 
 The unit stayed at U = 4 blocks (the 8-block unit lost its gate), so the
 boundaries are: R = 4, the round the old in-block wait stood at (and 5, the
@@ -16,6 +17,8 @@ import hashlib
 
 import numpy as np
 import pytest
+
+import launch_stats as LS
 
 pytestmark = pytest.mark.gpu
 
@@ -71,10 +74,14 @@ def check(pkg, torch, monkeypatch, host, off, lens, what):
     for mode, (kernel, env) in MODES.items():
         set_env(monkeypatch, env)
         dig = torch.zeros((n, 20), dtype=torch.uint8, device="cuda")
+        before = LS.snapshot()
         pkg.hash_device(d_host, d_off, d_len, dig, kernel=kernel)
         torch.cuda.synchronize()
+        launched = LS.delta(before)
         bad = np.flatnonzero((dig.cpu().numpy() != want).any(axis=1))
         assert bad.size == 0, f"{what}, {mode}: {bad.size} of {n} digests differ, first {bad[:8].tolist()}"
+        # both arms ran the quad shape and no other hash kernel (n <= 64 here: no sort either)
+        assert launched == LS.expect(quad=1), f"{what}, {mode}: launched {launched}"
 
 
 def test_block_counts_are_the_boundaries():

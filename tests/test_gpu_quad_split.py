@@ -4,11 +4,15 @@ and through AUTO (which picks it up to 16 chunks per CU), bit-exact against
 hashlib.sha1: partial and whole groups, every padding case, several consumer
 iterations plus a masked tail, lanes of one group ending at different blocks,
 byte-misaligned chunks, the dispatch rule at its own chunk count and its
-neighbour, and a non-IV initial state (batched SHA1Update)."""
+neighbour, and a non-IV initial state (batched SHA1Update).  That the forced
+and the AUTO call ran the quad shape (and the neighbour count the 4-block-unit
+shape) is read from the backend's launch counters (launch_stats.py)."""
 import hashlib
 
 import numpy as np
 import pytest
+
+import launch_stats as LS
 
 pytestmark = pytest.mark.gpu
 
@@ -53,6 +57,7 @@ def check(pkg, torch, monkeypatch, host, off, lens, what, uniform=None):
     for mode, (kernel, env) in MODES.items():
         set_env(monkeypatch, env)
         dig = torch.zeros((n, 20), dtype=torch.uint8, device="cuda")
+        before = LS.snapshot()
         if uniform is not None:
             pkg.hash_uniform_device(d_host, uniform, n, dig, kernel=kernel)
         else:
@@ -60,8 +65,11 @@ def check(pkg, torch, monkeypatch, host, off, lens, what, uniform=None):
             d_len = torch.from_numpy(lens.astype(np.int32)).cuda()
             pkg.hash_device(d_host, d_off, d_len, dig, kernel=kernel)
         torch.cuda.synchronize()
+        launched = LS.delta(before)
         bad = np.flatnonzero((dig.cpu().numpy() != want).any(axis=1))
         assert bad.size == 0, f"{what}, {mode}: {bad.size} of {n} digests differ, first {bad[:8].tolist()}"
+        # both arms ran the quad shape and no other hash kernel (n <= 64 here: no sort either)
+        assert launched == LS.expect(quad=1), f"{what}, {mode}: launched {launched}"
 
 
 def placed(rng, lens, mis):
@@ -110,10 +118,17 @@ def test_dispatch_boundary(pkg, dev, monkeypatch, n):
     want = sha1_rows(host, np.arange(n, dtype=np.uint64) * np.uint64(L), lens)
     set_env(monkeypatch, {})
     dig = torch.zeros((n, 20), dtype=torch.uint8, device="cuda")
-    pkg.hash_uniform_device(torch.from_numpy(host).cuda(), L, n, dig, kernel="auto")
+    d_host = torch.from_numpy(host).cuda()
+    before = LS.snapshot()
+    pkg.hash_uniform_device(d_host, L, n, dig, kernel="auto")
     torch.cuda.synchronize()
+    launched = LS.delta(before)
     bad = np.flatnonzero((dig.cpu().numpy() != want).any(axis=1))
     assert bad.size == 0, f"AUTO, {n} x {L} B: {bad.size} digests differ, first {bad[:8].tolist()}"
+    # which shape ran (csrc/sha1_runtime.hip split_unit; tests/test_gpu_dispatch.py has the whole table)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert cus == 256 and LS.drain_cus() == 0, (cus, LS.drain_cus())
+    assert launched == LS.expect(**{"quad" if n == 4096 else "unit4": 1}), f"AUTO, {n} chunks: launched {launched}"
 
 
 @pytest.mark.parametrize("mode", list(MODES))

@@ -28,6 +28,7 @@ KERNEL_ENVS = {
     "unit1": {"SHA1CHUNK_SPLIT_UNIT": "1"},
     "unit4": {"SHA1CHUNK_SPLIT_UNIT": "4"},
     "unit11": {"SHA1CHUNK_SPLIT_UNIT": "11"},
+    "unit416": {"SHA1CHUNK_SPLIT_UNIT": "416"},
 }
 
 

@@ -26,6 +26,7 @@ bool split_unit_study_built(int u) {
 hipError_t launch_split_study(const BatchArgs& A, int unit, hipStream_t st) {
     if (A.n == 0) return hipSuccess;
     const uint32_t groups = (A.n + 63u) / 64u;
+    if (split_unit_study_built(unit)) count_launch(kLaunchStudy);
     switch (unit) {
     case 2: launch_shape<2, 1>(A, groups, st); break;
     case 3: launch_shape<3, 1>(A, groups, st); break;

@@ -9,6 +9,8 @@
 #include <cstdio>
 #include <vector>
 
+void count_launch(LaunchCounter) {}  // the library's launch counters (rt_device.hip) are not linked here
+
 __global__ __launch_bounds__(1024) void sim_probe(const uint32_t* gblocks, const uint8_t* grun, uint32_t G, uint32_t H,
                                                   uint32_t F, uint32_t ncand, uint64_t* cyc, float* out) {
     __shared__ uint32_t blocks[kSimMaxG];  // as the planner keeps them: the run in bits 28-31
