@@ -9,11 +9,11 @@ from .sha1chunk import (SHA1, SHA1Context, Sha1ChunkError, binary2hex, device_co
                         get_chunk_hash, hash_batch, hash_device, hash_uniform_device,
                         hex2binary, lib, make_chunks, set_device, shahash,
                         synth_fill_device, verify_batch, verify_hash, VerifyQueue,
-                        ProgressiveVerifier)
+                        ProgressiveVerifier, DigestIndex, has_chunks)
 
 __all__ = [
     "SHA1", "SHA1Context", "Sha1ChunkError", "binary2hex", "device_count", "get_chunk_hash",
     "hash_batch", "hash_device", "hash_uniform_device", "hex2binary", "lib", "make_chunks",
     "set_device", "shahash", "synth_fill_device", "verify_batch", "verify_hash", "VerifyQueue",
-    "ProgressiveVerifier",
+    "ProgressiveVerifier", "DigestIndex", "has_chunks",
 ]

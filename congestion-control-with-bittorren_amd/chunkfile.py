@@ -6,6 +6,8 @@ Parse/emit compatibility only -- no hashing happens here:
     read_chunk(path)                      chunk.c:93-115       hash column of a chunk file
     find_chunk_idx_from_hash(hex, path)   chunk.c:123-160      index of a hash in a
                                                                chunk / master-chunk file
+    read_ids(path)                        (no counterpart)     (index, hash) of every line,
+                                                               the master header's included
 
 Formats the reference reads: ``<idx> <40-hex>`` lines (``tmp/*.chunks``,
 ``tmp/*.haschunks``; the shipped fixtures use CRLF line ends) and the master
@@ -76,3 +78,24 @@ def find_chunk_idx_from_hash(chunk_hash: str, hash_chunk_file: str | os.PathLike
             if len(toks) >= 2 and _hex_matches(toks[1], chunk_hash):
                 return int(toks[0])
     raise KeyError(f"{chunk_hash} not in {hash_chunk_file}")
+
+
+def read_ids(path: str | os.PathLike) -> list[tuple[int, str]]:
+    """(index, 40-hex digest) of every entry of a chunk or master-chunk file,
+    in file order: the ``<idx> <hex>`` lines, and the master file's header
+    line (``File: <path> Chunks:<i> <hex>``), which carries chunk <i>.  CRLF
+    line ends are dropped; other lines are skipped.  What sha1chunk.has_chunks
+    builds its index from."""
+    out = []
+    with open(path, "r", newline="") as f:
+        for line in f:
+            toks = line.split()
+            if len(toks) >= 2 and toks[0].isdigit():
+                idx, hx = int(toks[0]), toks[1]
+            elif len(toks) >= 4 and toks[2].startswith("Chunks:") and toks[2][len("Chunks:"):].isdigit():
+                idx, hx = int(toks[2][len("Chunks:"):]), toks[3]
+            else:
+                continue
+            if len(hx) >= 40:
+                out.append((idx, hx[:40].lower()))
+    return out

@@ -6,7 +6,8 @@
  * and the sha1chunk_* batch API of include/sha1chunk.h.  It depends on libc
  * alone.  Every call that reaches the GPU is forwarded to the HIP backend,
  * libsha1chunk_hip.so (the host runtime -- rt_device.hip, sha1_runtime.hip,
- * rt_file.hip, vq.hip, vq_persistent.hip, sha1_pv.hip, rt_update.hip -- + the gfx950 kernels;
+ * rt_file.hip, vq.hip, vq_persistent.hip, sha1_pv.hip, rt_update.hip, rt_gather.hip,
+ * rt_index.hip -- + the gfx950 kernels;
  * it exports its s1be_* entry points only, backend.map), which this
  * file dlopen()s from its own directory on the first such call -- so a
  * process that only makes single-message host calls (below) never loads the
@@ -113,6 +114,14 @@ static int fail(int code, const char *fmt, ...) {
                                const uint32_t *, size_t, uint8_t *, unsigned))                    \
     X(int, verify_gather_batch, (const void *, const uint64_t *, const uint32_t *, size_t,        \
                                  const uint32_t *, size_t, const uint8_t *, uint8_t *, unsigned)) \
+    X(void *, index_create, (const uint8_t *, size_t, unsigned))                                  \
+    X(void, index_destroy, (void *))                                                              \
+    X(size_t, index_size, (const void *))                                                         \
+    X(int, index_lookup_device_async, (const void *, const uint8_t *, size_t, uint32_t *, void *)) \
+    X(int, index_lookup, (const void *, const uint8_t *, size_t, uint32_t *))                     \
+    X(int, match_batch, (const void *, const void *, const uint64_t *, const uint32_t *, size_t,  \
+                         uint32_t *, unsigned))                                                   \
+    X(long, match_fd, (const void *, int, uint32_t *, size_t, size_t *))                          \
     X(int, device_count, (void))                                                                  \
     X(int, set_device, (int))                                                                     \
     X(int, device_pci_bus_id, (int, char *, size_t))                                              \
@@ -1009,4 +1018,85 @@ FE_API int sha1chunk_verify_gather_batch(const void *base, const uint64_t *seg_o
     if (rc) return rc;
     FORWARD(int, verify_gather_batch(base, seg_offsets, seg_lengths, n_segments, seg_first, n, expected, mismatch,
                                      flags));
+}
+
+/* ------------------------------------------------------------ digest index -- */
+/* A sha1chunk_index is the backend's object itself.  Always on the gfx950
+ * kernels: there is no host hash map (include/sha1chunk.h, "Digest index").
+ * The refusals that need no device are made here, before the backend is
+ * loaded, and leave the outputs alone. */
+#define LOOKUP_MAX (0xffffffffu - 255u) /* one lane per query, whole workgroups of 256 */
+#define INDEX_MAX ((size_t)1 << 31)
+
+FE_API sha1chunk_index *sha1chunk_index_create(const uint8_t *digests, size_t m, unsigned flags) {
+    if (check_batch_flags(flags)) return NULL;
+    if (m > INDEX_MAX) {
+        fail(SHA1CHUNK_EINVAL, "index of %zu digests: at most 2^31", m);
+        return NULL;
+    }
+    if (m && !digests) {
+        fail(SHA1CHUNK_EINVAL, "null pointer");
+        return NULL;
+    }
+    if (m && ((uintptr_t)digests & 3u)) {
+        fail(SHA1CHUNK_EALIGN, "digest array must be 4-byte aligned");
+        return NULL;
+    }
+    if (backend_dev()) return NULL;
+    void *ix = BE.index_create(digests, m, flags);
+    if (!ix) fail(SHA1CHUNK_ENOMEM, "%s", BE.last_error());
+    return (sha1chunk_index *)ix;
+}
+
+FE_API void sha1chunk_index_destroy(sha1chunk_index *ix) {
+    if (!ix || backend()) return;
+    BE.index_destroy(ix);
+}
+
+FE_API size_t sha1chunk_index_size(const sha1chunk_index *ix) {
+    if (!ix || backend()) return 0;
+    return BE.index_size(ix);
+}
+
+/* A lookup's refusals: a NULL index, then (n == 0 being a no-op) the count,
+ * NULL arrays and misaligned ones. */
+static int check_lookup(const void *ix, const void *digests, size_t n, const void *ids) {
+    if (!ix) return fail(SHA1CHUNK_EINVAL, "null index");
+    if (n > LOOKUP_MAX) return fail(SHA1CHUNK_EINVAL, "n too large: at most 2^32 - 256 per call");
+    if (n && (!digests || !ids)) return fail(SHA1CHUNK_EINVAL, "null pointer");
+    if (n && (((uintptr_t)digests | (uintptr_t)ids) & 3u))
+        return fail(SHA1CHUNK_EALIGN, "digest and id arrays must be 4-byte aligned");
+    return SHA1CHUNK_OK;
+}
+
+FE_API int sha1chunk_index_lookup_device_async(const sha1chunk_index *ix, const uint8_t *d_digests, size_t n,
+                                               uint32_t *d_ids, void *stream) {
+    int rc = check_lookup(ix, d_digests, n, d_ids);
+    if (rc) return rc;
+    FORWARD(int, index_lookup_device_async(ix, d_digests, n, d_ids, stream));
+}
+
+FE_API int sha1chunk_index_lookup(const sha1chunk_index *ix, const uint8_t *digests, size_t n, uint32_t *ids) {
+    int rc = check_lookup(ix, digests, n, ids);
+    if (rc) return rc;
+    FORWARD(int, index_lookup(ix, digests, n, ids));
+}
+
+FE_API int sha1chunk_match_batch(const sha1chunk_index *ix, const void *base, const uint64_t *offsets,
+                                 const uint32_t *lengths, size_t n, uint32_t *ids, unsigned flags) {
+    if (!ix) return fail(SHA1CHUNK_EINVAL, "null index");
+    int rc = check_batch_flags(flags);
+    if (rc) return rc;
+    if (n > BATCH_MAX) return fail(SHA1CHUNK_EINVAL, "n too large");
+    if (n && (!base || !offsets || !lengths || !ids)) return fail(SHA1CHUNK_EINVAL, "null pointer");
+    if (n && ((uintptr_t)ids & 3u)) return fail(SHA1CHUNK_EALIGN, "id array must be 4-byte aligned");
+    FORWARD(int, match_batch(ix, base, offsets, lengths, n, ids, flags));
+}
+
+FE_API long sha1chunk_match_fd(const sha1chunk_index *ix, int fd, uint32_t *ids, size_t max_chunks,
+                               size_t *total_chunks) {
+    if (!ix) return fail(SHA1CHUNK_EINVAL, "null index");
+    if (max_chunks && !ids) return fail(SHA1CHUNK_EINVAL, "null pointer");
+    if (max_chunks && ((uintptr_t)ids & 3u)) return fail(SHA1CHUNK_EALIGN, "id array must be 4-byte aligned");
+    FORWARD(long, match_fd(ix, fd, ids, max_chunks, total_chunks));
 }

@@ -199,6 +199,27 @@ struct GatherArgs {
 hipError_t launch_gather_scan(const GatherArgs& G, hipStream_t st);
 hipError_t launch_gather_copy(const GatherArgs& G, hipStream_t st);
 
+// The digest index (sha1_index.hip, arithmetic in index_map.hpp; host side in
+// rt_index.hip): an open-addressed array of `mask + 1` position words over a
+// table of m digests of five words each.
+struct IndexArgs {
+    const uint32_t* table;  // m x 5 words, read only
+    uint32_t m;             // at most 2^31
+    uint32_t* slots;        // mask + 1 words; 0xFFFFFFFF = empty
+    uint32_t mask;
+    // the build's counters, zeroed before it: the longest probe in slots
+    // visited, entries whose digest was in place already, entries whose probe
+    // wrapped past the last slot
+    unsigned long long* stats;
+};
+// One lane per table entry; the slots hold 0xFFFFFFFF and the counters 0.
+hipError_t launch_index_build(const IndexArgs& X, hipStream_t st);
+// One lane per query of five words: ids[i] = the lowest position of
+// queries[5i .. 5i+4] in the table, or 0xFFFFFFFF (n at most 2^32 - 256).
+// Only after the build is complete.
+hipError_t launch_index_lookup(const IndexArgs& X, const uint32_t* queries, uint32_t n, uint32_t* ids,
+                               hipStream_t st);
+
 // One workgroup of kSynthThreads per chunk.  A launch holds fewer than 2^32
 // work-items per dimension (the dispatch packet's grid size is a 32-bit count
 // of work-items), so one call fills at most kSynthMaxChunks chunks; a larger

@@ -1,6 +1,6 @@
 // sha1_runtime_internal.h -- the internal header of the backend's host side
 // (rt_device.hip, sha1_runtime.hip, rt_file.hip, vq.hip, vq_persistent.hip,
-// sha1_pv.hip, rt_update.hip, rt_gather.hip): the thread's error text and device, the device table and its
+// sha1_pv.hip, rt_update.hip, rt_gather.hip, rt_index.hip): the thread's error text and device, the device table and its
 // pipeline slots, host CPU placement, kernel choice and checked launches, and
 // what the verify queues and the progressive verifier share.  All of it is
 // internal to libsha1chunk_hip.so: the library exports its s1be_* entry

@@ -41,6 +41,7 @@ SEED = 0x5EED0001
 
 OK, EINVAL, ENODEV, ENOMEM, EHIP, EALIGN, EIO = 0, -1, -2, -3, -4, -5, -6
 HOST, DEVICE, ALL_DEVICES = 0, 1, 2
+NO_MATCH = 0xFFFFFFFF
 KERNEL_AUTO, KERNEL_LANE, KERNEL_FUSED, KERNEL_SPLIT = 0, 1, 2, 3
 KERNELS = {"auto": KERNEL_AUTO, "lane": KERNEL_LANE, "fused": KERNEL_FUSED, "split": KERNEL_SPLIT}
 
@@ -129,6 +130,13 @@ _SIGNATURES = [
      [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, C.c_uint64, _vp, _vp]),
     ("sha1chunk_hash_gather_batch", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint]),
     ("sha1chunk_verify_gather_batch", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, C.c_uint]),
+    ("sha1chunk_index_create", C.c_void_p, [_vp, C.c_size_t, C.c_uint]),
+    ("sha1chunk_index_destroy", None, [_vp]),
+    ("sha1chunk_index_size", C.c_size_t, [_vp]),
+    ("sha1chunk_index_lookup_device_async", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
+    ("sha1chunk_index_lookup", C.c_int, [_vp, _vp, C.c_size_t, _vp]),
+    ("sha1chunk_match_batch", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_uint]),
+    ("sha1chunk_match_fd", C.c_long, [_vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("sha1chunk_device_count", C.c_int, []),
     ("sha1chunk_set_device", C.c_int, [C.c_int]),
     ("sha1chunk_get_device", C.c_int, []),
@@ -773,6 +781,143 @@ def verify_gather(base, messages, expected) -> np.ndarray:
                                                first.size - 1, exp.ctypes.data, out.ctypes.data, flags),
            "sha1chunk_verify_gather_batch")
     return out
+
+
+# ---- digest index: match chunk digests against a chunk list ----
+def _digest_rows(digests) -> np.ndarray:
+    """Host digests -- an (n, 20) uint8 array, or a sequence of 20-byte
+    strings -- as one contiguous (n, 20) uint8 array."""
+    if isinstance(digests, np.ndarray):
+        a = np.ascontiguousarray(digests, np.uint8)
+    else:
+        a = np.frombuffer(b"".join(bytes(d) for d in digests), np.uint8)
+    if a.size % DIGEST_LEN:
+        raise ValueError("digests must hold 20 bytes each")
+    return a.reshape(-1, DIGEST_LEN)
+
+
+class DigestIndex:
+    """A set of m known digests on the device, queried with digests and
+    answering with positions (sha1chunk_index, include/sha1chunk.h): digest p
+    of `digests` has position p, a lookup gives the lowest position that holds
+    a queried digest or NO_MATCH.  `digests`: an (m, 20) uint8 array or a
+    sequence of 20-byte strings in host memory, or a torch CUDA uint8 tensor
+    (complete before the call) with m given or taken from its size.  The index
+    belongs to the device current at the call."""
+
+    def __init__(self, digests, m: int | None = None):
+        if hasattr(digests, "data_ptr"):
+            keep, flags = digests, DEVICE if digests.is_cuda else HOST
+            m = digests.numel() * digests.element_size() // DIGEST_LEN if m is None else m
+            addr = digests.data_ptr()
+        else:
+            keep, flags = _digest_rows(digests), HOST
+            m = keep.shape[0] if m is None else m
+            addr = keep.ctypes.data
+        self._ix = lib().sha1chunk_index_create(addr if m else None, m, flags)
+        del keep  # the index owns a copy
+        if not self._ix:
+            raise Sha1ChunkError(ENODEV if device_count() == 0 else EINVAL, "sha1chunk_index_create",
+                                 lib().sha1chunk_last_error().decode(errors="replace"))
+
+    @property
+    def size(self) -> int:
+        return int(lib().sha1chunk_index_size(self._ix))
+
+    def __len__(self) -> int:
+        return self.size
+
+    def lookup(self, digests) -> np.ndarray:
+        """sha1chunk_index_lookup of host digests -> n uint32 positions."""
+        q = _digest_rows(digests)
+        ids = np.full(q.shape[0], NO_MATCH, np.uint32)
+        _check(lib().sha1chunk_index_lookup(self._ix, q.ctypes.data, q.shape[0], ids.ctypes.data),
+               "sha1chunk_index_lookup")
+        return ids
+
+    def lookup_device(self, digests, ids, n: int | None = None, stream=None) -> None:
+        """Enqueue sha1chunk_index_lookup_device_async: digests a torch CUDA
+        uint8 tensor of n x 20 bytes, ids one of n int32 (the uint32 positions)."""
+        n = ids.numel() if n is None else n
+        _check(lib().sha1chunk_index_lookup_device_async(self._ix, _addr(digests), n, _addr(ids), _stream_ptr(stream)),
+               "sha1chunk_index_lookup_device_async")
+
+    def match_batch(self, base, offsets, lengths, ids=None):
+        """sha1chunk_match_batch: the position of every chunk's digest.  Host
+        form (base bytes or a numpy array, offsets and lengths sequences)
+        -> n uint32 positions; device form (torch CUDA tensors: base uint8,
+        offsets int64, lengths int32, and ids int32 to receive the positions)
+        -> ids."""
+        if hasattr(base, "data_ptr"):
+            if ids is None:
+                raise ValueError("the device form needs an ids tensor")
+            _check(lib().sha1chunk_match_batch(self._ix, _addr(base), _addr(offsets), _addr(lengths), offsets.numel(),
+                                               _addr(ids), DEVICE), "sha1chunk_match_batch")
+            return ids
+        b = np.frombuffer(base, np.uint8) if isinstance(base, (bytes, bytearray)) else \
+            np.ascontiguousarray(base).view(np.uint8).reshape(-1)
+        if b.size == 0:
+            b = np.zeros(1, np.uint8)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint32)
+        if off.shape != ln.shape:
+            raise ValueError("offsets and lengths differ in length")
+        out = np.full(off.size, NO_MATCH, np.uint32)
+        _check(lib().sha1chunk_match_batch(self._ix, b.ctypes.data, off.ctypes.data, ln.ctypes.data, off.size,
+                                           out.ctypes.data, HOST), "sha1chunk_match_batch")
+        return out
+
+    def match_fd(self, src, max_chunks: int | None = None) -> np.ndarray:
+        """sha1chunk_match_fd: the position of every 512 KiB chunk of a file
+        (a path, a binary file object on a real fd, or an fd) from its offset
+        on -> uint32 positions, at most max_chunks of them."""
+        if isinstance(src, (str, os.PathLike)):
+            with open(src, "rb") as f:
+                return self.match_fd(f, max_chunks)
+        if isinstance(src, int):
+            fd = src
+        else:
+            fd = src.fileno()
+            os.lseek(fd, src.tell(), os.SEEK_SET)
+        if max_chunks is None:
+            size = os.fstat(fd).st_size - os.lseek(fd, 0, os.SEEK_CUR)
+            max_chunks = max((size + CHUNK_LEN - 1) // CHUNK_LEN, 1)
+        ids = np.full(max_chunks, NO_MATCH, np.uint32)
+        total = C.c_size_t(0)
+        n = _check(lib().sha1chunk_match_fd(self._ix, fd, ids.ctypes.data, max_chunks, C.byref(total)),
+                   "sha1chunk_match_fd")
+        return ids[:n]
+
+    def close(self) -> None:
+        if self._ix:
+            lib().sha1chunk_index_destroy(self._ix)
+            self._ix = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def has_chunks(data_path, chunk_list_path) -> list[tuple[int, bytes]]:
+    """Which chunks of a chunk list a data file holds: (id in the list,
+    digest) for every 512 KiB chunk of `data_path` whose digest is in
+    `chunk_list_path` (a plain chunk file, or a master chunk file with its
+    header line), in file order -- the lines of the peer's has-chunks file
+    (the reference's tmp/B.haschunks: B.tar under ids 2 and 3 of
+    C.masterchunks).  A digest listed under several ids gets the lowest."""
+    from . import chunkfile
+    entries = sorted(chunkfile.read_ids(chunk_list_path))
+    with DigestIndex([bytes.fromhex(h) for _, h in entries]) as ix:
+        pos = ix.match_fd(data_path)
+    return [(entries[p][0], bytes.fromhex(entries[p][1])) for p in pos.tolist() if p != NO_MATCH]
 
 
 def synth_fill_device(dst, first: int, count: int, chunk_len: int = CHUNK_LEN, seed: int = SEED,

@@ -608,6 +608,107 @@ int sha1chunk_verify_gather_batch(const void *base, const uint64_t *seg_offsets,
                                   const uint32_t *seg_first, size_t n, const uint8_t *expected,
                                   uint8_t *mismatch, unsigned flags);
 
+/* ---- Digest index: match chunk digests against a chunk list ---------------
+ * Every path above ends in 20-byte digests, or in "does digest i equal
+ * expected digest i".  The peer also asks which chunk a digest IS: it answers
+ * a WHOHAS by looking each requested hash up in its has-chunks list and serves
+ * a GET by find_chunk_idx_from_hash, a scan of the text file per call; and a
+ * peer that holds a data file and the master list needs the has-chunks file
+ * that names the file's chunks by their master ids (the reference's
+ * tmp/B.haschunks: B.tar's two digests under ids 2 and 3 of C.masterchunks).
+ * Both are one primitive: a set of m known digests, queried with n digests,
+ * answering with positions.  It runs on the device because that is where the
+ * digests are after the hash calls above: a lookup queued on the same stream
+ * needs no synchronise between hash and match and returns 4 bytes per chunk.
+ *
+ * An index is built once over a table of m digests -- digest p has position p
+ * -- and is immutable afterwards.  A lookup answers, for every queried digest,
+ * the lowest position that holds it, or SHA1CHUNK_NO_MATCH.
+ *
+ * Table size.  m may be 0; every lookup then answers SHA1CHUNK_NO_MATCH.
+ *   m <= 2^31 (SHA1CHUNK_EINVAL above).
+ * Duplicates.  Duplicate digests in the table are legal and the lowest
+ *   position wins: a sparse file has thousands of identical all-zero chunks,
+ *   and the reference's find_chunk_idx_from_hash returns the first match too.
+ * Device.  An index belongs to the device that was current at create.  A call
+ *   made with another device current is SHA1CHUNK_EINVAL.
+ *   SHA1CHUNK_ALL_DEVICES is SHA1CHUNK_EINVAL in create and in match_batch.
+ * Completion.  create copies the table into memory the index owns, builds on a
+ *   stream of the library's own and waits for it; afterwards any stream and
+ *   any thread may look up.  A SHA1CHUNK_DEVICE table must be complete before
+ *   the call.  Lookups from several threads at once are allowed (host-array
+ *   calls on one device take turns).  destroy must not overlap another call.
+ * Alignment and count.  Digest and id arrays are 4-byte aligned, as digest
+ *   buffers are elsewhere (SHA1CHUNK_EALIGN).  n <= 2^32 - 256 per lookup, as
+ *   for the compare kernel; n <= 2^32 - 1025 for match_batch, as for every
+ *   batch that is hashed.
+ * Refusals.  A refused call writes nothing to its outputs.  A NULL index,
+ *   NULL arrays with n > 0, SHA1CHUNK_ALL_DEVICES or unknown flags and n too
+ *   large are SHA1CHUNK_EINVAL; these and misalignment are refused before the
+ *   backend is loaded.  n == 0 with a valid index is a successful no-op.
+ * Routing.  The host forms go through the device: stage up, kernel, 4 n bytes
+ *   back.  There is no host hash map and no routing knob
+ *   (SHA1CHUNK_HOST_SMALL does not apply); a gfx950 device is required, as
+ *   everywhere else, and without one the calls return SHA1CHUNK_ENODEV.
+ * Paths of the match forms.  match_batch(SHA1CHUNK_HOST) and match_fd run the
+ *   hash paths of sha1chunk_hash_batch and sha1chunk_hash_fd on the kernels,
+ *   unchanged, and then look the digests up.  match_batch(SHA1CHUNK_DEVICE)
+ *   does what sha1chunk_verify_batch(SHA1CHUNK_DEVICE) does with the lookup
+ *   where the compare is: same stream, one synchronise; ids is a device array
+ *   then.  match_fd hashes from the fd's offset and leaves it where
+ *   sha1chunk_hash_fd would; it returns the number of ids written (at most
+ *   max_chunks) and *total_chunks (optional) gets the file's chunk count.
+ *
+ * Layout (csrc/sha1_index.hip, arithmetic in csrc/index_map.hpp).  An
+ *   open-addressed array of position words in device memory: the smallest
+ *   power of two >= 2 m slots, at least 8, so it is at most half full and
+ *   every probe sequence ends at an empty slot.  A digest's home slot is a
+ *   fixed integer mix of its first two words only; probing is linear; a slot
+ *   carries no tag, so every occupied probe compares all five words against
+ *   the table (a tag word per slot is a possible later optimisation).  The
+ *   build kernel runs one lane per entry and touches slots with agent-scope
+ *   atomics only; the lookup kernel is a later kernel with plain loads.
+ * Trust.  The table comes from local chunk files, which are trusted.  Digests
+ *   that share their first 8 bytes share a home slot: a hostile list degrades
+ *   the build and the lookups to linear chains and stays correct.
+ *
+ * Measured on MI355X (tools/index_bench.py, profiles/index.jsonl, DESIGN.md
+ * section 6; random digests, every query a hit, median (min-max) of 20
+ * repetitions in one run).  m = n = 16384 / 262144: create from device memory
+ * 0.054 (0.053-0.058) / 0.244 (0.239-0.275) ms wall clock; the lookup kernel
+ * alone 0.012 (0.012-0.017) / 0.072 (0.033-0.078) ms by HIP events; the host
+ * form 0.059 / 0.399 ms wall clock.  The same answer by copying the digests to
+ * the host and asking a Python dict: 0.96 / 74.3 ms, and 0.76 / 21.9 ms to
+ * build the dict.  Behind sha1chunk_hash_uniform_async on 4096 x 512 KiB (5.790
+ * ms, 5.777-5.814) the lookup adds 0.010 ms and the compare kernel -0.001 ms,
+ * both inside that spread.  Not measured: tables with long chains or many
+ * duplicates, misses, m above 262144, match_batch and match_fd, several
+ * devices. */
+#define SHA1CHUNK_NO_MATCH 0xFFFFFFFFu
+typedef struct sha1chunk_index sha1chunk_index;
+
+/* m digests of 20 bytes; digest p has position p.  flags: SHA1CHUNK_HOST or
+ * SHA1CHUNK_DEVICE (where `digests` lies).  Synchronous.  NULL on failure
+ * (sha1chunk_last_error() says why). */
+sha1chunk_index *sha1chunk_index_create(const uint8_t *digests, size_t m, unsigned flags);
+void sha1chunk_index_destroy(sha1chunk_index *ix); /* NULL is fine */
+size_t sha1chunk_index_size(const sha1chunk_index *ix); /* m; 0 for NULL */
+
+/* ids[i] = lowest position p with table[p] == digests[i], else SHA1CHUNK_NO_MATCH.
+ * Device arrays, asynchronous on `stream`; never waits for the device. */
+int sha1chunk_index_lookup_device_async(const sha1chunk_index *ix, const uint8_t *d_digests,
+                                        size_t n, uint32_t *d_ids, void *stream);
+/* The same for host arrays; synchronous. */
+int sha1chunk_index_lookup(const sha1chunk_index *ix, const uint8_t *digests, size_t n,
+                           uint32_t *ids);
+
+/* Hash, then look up: the arguments of sha1chunk_hash_batch, ids instead of digests. */
+int sha1chunk_match_batch(const sha1chunk_index *ix, const void *base, const uint64_t *offsets,
+                          const uint32_t *lengths, size_t n, uint32_t *ids, unsigned flags);
+/* The arguments of sha1chunk_hash_fd, ids instead of digests. */
+long sha1chunk_match_fd(const sha1chunk_index *ix, int fd, uint32_t *ids, size_t max_chunks,
+                        size_t *total_chunks);
+
 /* Device management. */
 int sha1chunk_device_count(void);
 int sha1chunk_set_device(int device);
