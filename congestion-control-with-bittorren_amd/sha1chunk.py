@@ -349,7 +349,7 @@ def hash_batch(base: np.ndarray | bytes, offsets: Sequence[int], lengths: Sequen
     return out
 
 
-def verify_batch(base, offsets, lengths, expected: np.ndarray) -> np.ndarray:
+def verify_batch(base, offsets, lengths, expected: np.ndarray, all_devices: bool = False) -> np.ndarray:
     """verify_hash() semantics per chunk: 0 = match, 1 = mismatch."""
     b = np.ascontiguousarray(np.frombuffer(base, np.uint8) if isinstance(base, (bytes, bytearray))
                              else base).view(np.uint8).reshape(-1)
@@ -357,8 +357,9 @@ def verify_batch(base, offsets, lengths, expected: np.ndarray) -> np.ndarray:
     ln = np.ascontiguousarray(lengths, np.uint32)
     exp = np.ascontiguousarray(expected, np.uint8).reshape(-1, DIGEST_LEN)
     mism = np.zeros(off.size, np.uint8)
+    flags = ALL_DEVICES if all_devices else HOST
     _check(lib().sha1chunk_verify_batch(b.ctypes.data, _np_ptr(off, _u64p), _np_ptr(ln, _u32p),
-                                        off.size, _np_ptr(exp), _np_ptr(mism), HOST),
+                                        off.size, _np_ptr(exp), _np_ptr(mism), flags),
            "sha1chunk_verify_batch")
     return mism
 
