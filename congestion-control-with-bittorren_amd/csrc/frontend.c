@@ -122,6 +122,12 @@ static int fail(int code, const char *fmt, ...) {
     X(int, match_batch, (const void *, const void *, const uint64_t *, const uint32_t *, size_t,  \
                          uint32_t *, unsigned))                                                   \
     X(long, match_fd, (const void *, int, uint32_t *, size_t, size_t *))                          \
+    X(int, index_reserve, (void *, size_t))                                                       \
+    X(size_t, index_capacity, (const void *))                                                     \
+    X(int, index_append_device_async, (void *, const uint8_t *, size_t, const uint8_t *, void *)) \
+    X(int, index_append, (void *, const uint8_t *, size_t, const uint8_t *))                      \
+    X(int, admit_batch, (void *, const void *, const uint64_t *, const uint32_t *, size_t,        \
+                         const uint8_t *, uint8_t *, unsigned))                                   \
     X(int, device_count, (void))                                                                  \
     X(int, set_device, (int))                                                                     \
     X(int, device_pci_bus_id, (int, char *, size_t))                                              \
@@ -1099,4 +1105,50 @@ FE_API long sha1chunk_match_fd(const sha1chunk_index *ix, int fd, uint32_t *ids,
     if (max_chunks && !ids) return fail(SHA1CHUNK_EINVAL, "null pointer");
     if (max_chunks && ((uintptr_t)ids & 3u)) return fail(SHA1CHUNK_EALIGN, "id array must be 4-byte aligned");
     FORWARD(long, match_fd(ix, fd, ids, max_chunks, total_chunks));
+}
+
+FE_API size_t sha1chunk_index_capacity(const sha1chunk_index *ix) {
+    if (!ix || backend()) return 0;
+    return BE.index_capacity(ix);
+}
+
+FE_API int sha1chunk_index_reserve(sha1chunk_index *ix, size_t capacity) {
+    if (!ix) return fail(SHA1CHUNK_EINVAL, "null index");
+    if (capacity > INDEX_MAX) return fail(SHA1CHUNK_EINVAL, "index of %zu digests: at most 2^31", capacity);
+    FORWARD(int, index_reserve(ix, capacity));
+}
+
+/* An append's refusals that need no look at the index: a NULL index, then
+ * (k == 0 being a no-op) the count, a NULL digest array and a misaligned one.
+ * The skip bytes may be absent and sit at any address. */
+static int check_append(const void *ix, const void *digests, size_t k) {
+    if (!ix) return fail(SHA1CHUNK_EINVAL, "null index");
+    if (k > LOOKUP_MAX) return fail(SHA1CHUNK_EINVAL, "k too large: at most 2^32 - 256 per call");
+    if (k && !digests) return fail(SHA1CHUNK_EINVAL, "null pointer");
+    if (k && ((uintptr_t)digests & 3u)) return fail(SHA1CHUNK_EALIGN, "digest array must be 4-byte aligned");
+    return SHA1CHUNK_OK;
+}
+
+FE_API int sha1chunk_index_append_device_async(sha1chunk_index *ix, const uint8_t *d_digests, size_t k,
+                                               const uint8_t *d_skip, void *stream) {
+    int rc = check_append(ix, d_digests, k);
+    if (rc) return rc;
+    FORWARD(int, index_append_device_async(ix, d_digests, k, d_skip, stream));
+}
+
+FE_API int sha1chunk_index_append(sha1chunk_index *ix, const uint8_t *digests, size_t k, const uint8_t *skip) {
+    int rc = check_append(ix, digests, k);
+    if (rc) return rc;
+    FORWARD(int, index_append(ix, digests, k, skip));
+}
+
+FE_API int sha1chunk_admit_batch(sha1chunk_index *ix, const void *base, const uint64_t *offsets,
+                                 const uint32_t *lengths, size_t n, const uint8_t *expected, uint8_t *mismatch,
+                                 unsigned flags) {
+    if (!ix) return fail(SHA1CHUNK_EINVAL, "null index");
+    int rc = check_batch_flags(flags);
+    if (rc) return rc;
+    if (n > BATCH_MAX) return fail(SHA1CHUNK_EINVAL, "n too large");
+    if (n && (!base || !offsets || !lengths || !expected || !mismatch)) return fail(SHA1CHUNK_EINVAL, "null pointer");
+    FORWARD(int, admit_batch(ix, base, offsets, lengths, n, expected, mismatch, flags));
 }

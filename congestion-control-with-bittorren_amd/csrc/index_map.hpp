@@ -25,6 +25,15 @@
 // once may have been lowered since, but only to another position of the same
 // digest, so the comparison's answer stands and racing lanes build the same
 // array, whatever their order.
+//
+// The set grows after the build (include/sha1chunk.h, "Digest index"): the
+// table has room for `capacity` digests, the array slots_for(capacity) slots,
+// and appended entries are inserted by the same insert().  An appended entry
+// may be skipped: its row is written, it is never inserted, and as nothing
+// but a slot leads to a row, no lookup answers it.  A larger array is filled
+// from a smaller one by rehash_slot(): the old slots hold exactly the admitted
+// distinct digests at their lowest positions, so inserting what they hold
+// rebuilds the set without a record of which rows were skipped.
 #pragma once
 
 #include <stdint.h>
@@ -103,6 +112,15 @@ S1IX_HD inline uint32_t lookup(const Slots& slots, uint32_t mask, const uint32_t
         const uint32_t held = slots.load(h);
         if (held == kEmpty || same_digest(table + static_cast<uint64_t>(kWords) * held, w)) return held;
     }
+}
+
+// Growth: what slot s of the old array holds, inserted into the new array over
+// the same table rows.  Old: uint32_t load(s); New: claim and lower.
+template <class Old, class New>
+S1IX_HD inline void rehash_slot(const Old& old_slots, uint32_t s, const New& new_slots, uint32_t new_mask,
+                                const uint32_t* table) {
+    const uint32_t p = old_slots.load(s);
+    if (p != kEmpty) (void)insert(new_slots, new_mask, table, p);
 }
 
 // The sequential slot array of the host check.

@@ -220,6 +220,16 @@ hipError_t launch_index_build(const IndexArgs& X, hipStream_t st);
 hipError_t launch_index_lookup(const IndexArgs& X, const uint32_t* queries, uint32_t n, uint32_t* ids,
                                hipStream_t st);
 
+// One lane per appended entry: table row base + i, i < k, is inserted unless
+// skip (k bytes, or null) says skip[i] != 0.  The rows were written by an
+// earlier operation on the stream; base + k <= 2^31; X.stats points at the
+// counters this launch adds to (the build's three, in the same order).
+hipError_t launch_index_append(const IndexArgs& X, uint32_t base, uint32_t k, const uint8_t* skip, hipStream_t st);
+// Growth: one lane per slot of a finished array of old_mask + 1 words; what it
+// holds is inserted into X.slots (emptied before) over X.table, which holds
+// every row the old table held.  Counts nothing.
+hipError_t launch_index_rehash(const IndexArgs& X, const uint32_t* old_slots, uint32_t old_mask, hipStream_t st);
+
 // One workgroup of kSynthThreads per chunk.  A launch holds fewer than 2^32
 // work-items per dimension (the dispatch packet's grid size is a 32-bit count
 // of work-items), so one call fills at most kSynthMaxChunks chunks; a larger

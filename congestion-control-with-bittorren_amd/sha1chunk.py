@@ -135,6 +135,11 @@ _SIGNATURES = [
     ("sha1chunk_index_size", C.c_size_t, [_vp]),
     ("sha1chunk_index_lookup_device_async", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
     ("sha1chunk_index_lookup", C.c_int, [_vp, _vp, C.c_size_t, _vp]),
+    ("sha1chunk_index_reserve", C.c_int, [_vp, C.c_size_t]),
+    ("sha1chunk_index_capacity", C.c_size_t, [_vp]),
+    ("sha1chunk_index_append_device_async", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
+    ("sha1chunk_index_append", C.c_int, [_vp, _vp, C.c_size_t, _vp]),
+    ("sha1chunk_admit_batch", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_uint]),
     ("sha1chunk_match_batch", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_uint]),
     ("sha1chunk_match_fd", C.c_long, [_vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("sha1chunk_device_count", C.c_int, []),
@@ -804,7 +809,10 @@ class DigestIndex:
     a queried digest or NO_MATCH.  `digests`: an (m, 20) uint8 array or a
     sequence of 20-byte strings in host memory, or a torch CUDA uint8 tensor
     (complete before the call) with m given or taken from its size.  The index
-    belongs to the device current at the call."""
+    belongs to the device current at the call.  The set grows by `append`,
+    `append_device` and `admit_batch`: digest i of a call gets position
+    size + i, and a digest whose skip byte is set uses its position up without
+    joining the set."""
 
     def __init__(self, digests, m: int | None = None):
         if hasattr(digests, "data_ptr"):
@@ -827,6 +835,65 @@ class DigestIndex:
 
     def __len__(self) -> int:
         return self.size
+
+    @property
+    def capacity(self) -> int:
+        return int(lib().sha1chunk_index_capacity(self._ix))
+
+    def reserve(self, capacity: int) -> None:
+        """sha1chunk_index_reserve: room for at least `capacity` digests."""
+        _check(lib().sha1chunk_index_reserve(self._ix, capacity), "sha1chunk_index_reserve")
+
+    def append(self, digests, skip=None) -> int:
+        """sha1chunk_index_append of host digests (skip: one byte per digest,
+        non-zero = not admitted, or None) -> the position of the first; grows
+        the index when it is full."""
+        q = _digest_rows(digests)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(-1)
+        if sk is not None and sk.size != q.shape[0]:
+            raise ValueError("digests and skip differ in length")
+        first = self.size
+        _check(lib().sha1chunk_index_append(self._ix, q.ctypes.data, q.shape[0], None if sk is None else sk.ctypes.data),
+               "sha1chunk_index_append")
+        return first
+
+    def append_device(self, digests, k: int | None = None, skip=None, stream=None) -> int:
+        """Enqueue sha1chunk_index_append_device_async: digests a torch CUDA
+        uint8 tensor of k x 20 bytes, skip one of k bytes or None -> the
+        position of the first.  Never grows: reserve first."""
+        k = digests.numel() * digests.element_size() // DIGEST_LEN if k is None else k
+        first = self.size
+        _check(lib().sha1chunk_index_append_device_async(self._ix, _addr(digests), k, _addr(skip), _stream_ptr(stream)),
+               "sha1chunk_index_append_device_async")
+        return first
+
+    def admit_batch(self, base, offsets, lengths, expected, mismatch=None):
+        """sha1chunk_admit_batch: verify every chunk against its expected
+        digest and append all digests with skip = mismatch, so that exactly the
+        verified chunks join the set.  Host form (base bytes or a numpy array,
+        offsets and lengths sequences, expected host digests) -> n mismatch
+        bytes; device form (torch CUDA tensors: base uint8, offsets int64,
+        lengths int32, expected uint8, and mismatch uint8 to receive the
+        verdicts) -> mismatch."""
+        if hasattr(base, "data_ptr"):
+            if mismatch is None:
+                raise ValueError("the device form needs a mismatch tensor")
+            _check(lib().sha1chunk_admit_batch(self._ix, _addr(base), _addr(offsets), _addr(lengths), offsets.numel(),
+                                               _addr(expected), _addr(mismatch), DEVICE), "sha1chunk_admit_batch")
+            return mismatch
+        b = np.frombuffer(base, np.uint8) if isinstance(base, (bytes, bytearray)) else \
+            np.ascontiguousarray(base).view(np.uint8).reshape(-1)
+        if b.size == 0:
+            b = np.zeros(1, np.uint8)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint32)
+        exp = _digest_rows(expected)
+        if off.shape != ln.shape or exp.shape[0] != off.size:
+            raise ValueError("offsets, lengths and expected differ in length")
+        out = np.zeros(off.size, np.uint8)
+        _check(lib().sha1chunk_admit_batch(self._ix, b.ctypes.data, off.ctypes.data, ln.ctypes.data, off.size,
+                                           exp.ctypes.data, out.ctypes.data, HOST), "sha1chunk_admit_batch")
+        return out
 
     def lookup(self, digests) -> np.ndarray:
         """sha1chunk_index_lookup of host digests -> n uint32 positions."""

@@ -621,9 +621,47 @@ int sha1chunk_verify_gather_batch(const void *base, const uint64_t *seg_offsets,
  * digests are after the hash calls above: a lookup queued on the same stream
  * needs no synchronise between hash and match and returns 4 bytes per chunk.
  *
- * An index is built once over a table of m digests -- digest p has position p
- * -- and is immutable afterwards.  A lookup answers, for every queried digest,
- * the lowest position that holds it, or SHA1CHUNK_NO_MATCH.
+ * An index is built over a table of m digests -- digest p has position p -- and
+ * grows by appends afterwards: the has-chunks set of a peer that is downloading
+ * gains a digest with every chunk it accepts (the reference's
+ * update_owned_chunks appends the hash to the has-chunks file, and
+ * process_whohas_packet reads the file again on the next WHOHAS).  A lookup
+ * answers, for every queried digest, the lowest admitted position that holds
+ * it, or SHA1CHUNK_NO_MATCH.
+ *
+ * Appends.  Digest i of an append gets position size_before + i.  Where the
+ *   call's skip array is not NULL and skip[i] != 0, the position is used up but
+ *   the digest is NOT admitted: no lookup ever answers it.  With skip = the
+ *   mismatch bytes of a compare, exactly the verified chunks join the set:
+ *   hash -> compare -> append(skip = mismatch) on one stream is the receive
+ *   path, with no trip to the host between the verdict and the set.
+ *   sha1chunk_admit_batch is that sequence in one call.
+ * Positions.  sha1chunk_index_size counts every position handed out, skipped
+ *   ones included.  The host therefore knows the size when it enqueues, without
+ *   asking the device, and several appends can be queued back to back.
+ * Lookups after appends.  A lookup still answers the lowest admitted position
+ *   of a digest.  Appending a digest that is already in the set uses up a
+ *   position and changes no answer.  A skipped digest that is admitted nowhere
+ *   else answers SHA1CHUNK_NO_MATCH; admitted later, it answers the later
+ *   position.
+ * Capacity.  An index has room for sha1chunk_index_capacity digests: m after
+ *   create.  The slot array always has the slot count of the Layout paragraph
+ *   for `capacity` digests, so it is never more than half full and every probe
+ *   ends.  sha1chunk_index_reserve and the host sha1chunk_index_append grow the
+ *   index (never shrink it); the host form at least doubles the capacity when
+ *   it is full.  The device form never allocates: if size + k > capacity it
+ *   returns SHA1CHUNK_EINVAL with an error text that names
+ *   sha1chunk_index_reserve, writes nothing and leaves the index as it was.
+ *   An index that is never appended to keeps its slot count and its answers.
+ * Ordering.  An append is a write to the index.  The caller orders it against
+ *   every lookup and every other append of that index as it would order a
+ *   write to a buffer: on the same stream, or through events.  The host forms
+ *   (append, lookup, admit_batch(SHA1CHUNK_HOST), match_*) take turns under the
+ *   device's mutex on one stream of the library's and may run from several
+ *   threads at once.  Two threads must not append through the device form at
+ *   once.  reserve, and a host append that grows, wait for the whole device
+ *   before they read and before they free the old arrays; like destroy, they
+ *   must not overlap a device-form call on the same index.
  *
  * Table size.  m may be 0; every lookup then answers SHA1CHUNK_NO_MATCH.
  *   m <= 2^31 (SHA1CHUNK_EINVAL above).
@@ -646,6 +684,12 @@ int sha1chunk_verify_gather_batch(const void *base, const uint64_t *seg_offsets,
  *   NULL arrays with n > 0, SHA1CHUNK_ALL_DEVICES or unknown flags and n too
  *   large are SHA1CHUNK_EINVAL; these and misalignment are refused before the
  *   backend is loaded.  n == 0 with a valid index is a successful no-op.
+ *   Of the appends: a NULL index, NULL digests with k > 0, k above the lookup
+ *   limit, a capacity or a total size above 2^31, SHA1CHUNK_ALL_DEVICES or
+ *   unknown flags in admit_batch and an index that belongs to another device
+ *   are SHA1CHUNK_EINVAL; digests that are not 4-byte aligned are
+ *   SHA1CHUNK_EALIGN.  skip and mismatch are bytes and may sit at any
+ *   alignment.  k == 0 is a successful no-op.
  * Routing.  The host forms go through the device: stage up, kernel, 4 n bytes
  *   back.  There is no host hash map and no routing knob
  *   (SHA1CHUNK_HOST_SMALL does not apply); a gfx950 device is required, as
@@ -658,6 +702,12 @@ int sha1chunk_verify_gather_batch(const void *base, const uint64_t *seg_offsets,
  *   then.  match_fd hashes from the fd's offset and leaves it where
  *   sha1chunk_hash_fd would; it returns the number of ids written (at most
  *   max_chunks) and *total_chunks (optional) gets the file's chunk count.
+ *   admit_batch(SHA1CHUNK_DEVICE) is sha1chunk_verify_batch(SHA1CHUNK_DEVICE)'s
+ *   sequence with the append behind the compare: same stream, one synchronise,
+ *   expected and mismatch device arrays; it refuses when capacity is short, as
+ *   the device append does.  admit_batch(SHA1CHUNK_HOST) hashes as
+ *   sha1chunk_hash_batch does, compares, and appends through the host form,
+ *   which grows the index.
  *
  * Layout (csrc/sha1_index.hip, arithmetic in csrc/index_map.hpp).  An
  *   open-addressed array of position words in device memory: the smallest
@@ -667,7 +717,12 @@ int sha1chunk_verify_gather_batch(const void *base, const uint64_t *seg_offsets,
  *   carries no tag, so every occupied probe compares all five words against
  *   the table (a tag word per slot is a possible later optimisation).  The
  *   build kernel runs one lane per entry and touches slots with agent-scope
- *   atomics only; the lookup kernel is a later kernel with plain loads.
+ *   atomics only; the lookup kernel is a later kernel with plain loads.  The
+ *   append kernel is the build kernel with a base and a skip array; the rows
+ *   of a call are copied into the table by an earlier operation on the stream,
+ *   so no lane reads a row that its own launch wrote.  Growth copies the rows
+ *   and runs one lane per old slot, which inserts what the slot holds into the
+ *   new array: the old slots hold exactly the admitted digests.
  * Trust.  The table comes from local chunk files, which are trusted.  Digests
  *   that share their first 8 bytes share a home slot: a hostile list degrades
  *   the build and the lookups to linear chains and stays correct.
@@ -683,7 +738,25 @@ int sha1chunk_verify_gather_batch(const void *base, const uint64_t *seg_offsets,
  * ms, 5.777-5.814) the lookup adds 0.010 ms and the compare kernel -0.001 ms,
  * both inside that spread.  Not measured: tables with long chains or many
  * duplicates, misses, m above 262144, match_batch and match_fd, several
- * devices. */
+ * devices.
+ *
+ * Appends, measured on MI355X (tools/index_append_bench.py,
+ * profiles/index_append.jsonl; random digests, every one
+ * admitted, median (min-max) of 20 repetitions in one run, each on a fresh
+ * index of m digests).  k = 1 / 64 / 4096 digests appended to m = 262144:
+ * sha1chunk_index_append_device_async 0.008 (0.008-0.009) / 0.012
+ * (0.012-0.017) / 0.015 (0.014-0.018) ms by HIP events; the host form with
+ * room 0.026 / 0.030 / 0.038 ms wall clock; the host form that grows the index
+ * 0.442 / 0.458 / 0.465 ms; sha1chunk_index_destroy plus
+ * sha1chunk_index_create over the m + k digests from device memory, the only
+ * way before appends existed, 0.474 / 0.492 / 0.491 ms in the same run.  To
+ * m = 16384: 0.013 / 0.014 / 0.019 ms, 0.018 / 0.021 / 0.033 ms, 0.044 /
+ * 0.048 / 0.060 ms growing, against 0.040 / 0.039 / 0.040 ms for destroy plus
+ * create: at that size a growth costs as much as building anew, and more for
+ * k = 4096.  Every figure is tens of microseconds, a few launches' worth; the
+ * benefit is that the set follows the verdicts on the stream, not the time.
+ * Not measured: skip masks, duplicates, chains, appends behind a hash,
+ * admit_batch, create from host memory, several devices. */
 #define SHA1CHUNK_NO_MATCH 0xFFFFFFFFu
 typedef struct sha1chunk_index sha1chunk_index;
 
@@ -692,7 +765,22 @@ typedef struct sha1chunk_index sha1chunk_index;
  * (sha1chunk_last_error() says why). */
 sha1chunk_index *sha1chunk_index_create(const uint8_t *digests, size_t m, unsigned flags);
 void sha1chunk_index_destroy(sha1chunk_index *ix); /* NULL is fine */
-size_t sha1chunk_index_size(const sha1chunk_index *ix); /* m; 0 for NULL */
+/* Positions handed out: m plus every appended digest, skipped ones included; 0 for NULL. */
+size_t sha1chunk_index_size(const sha1chunk_index *ix);
+
+/* Room for at least `capacity` digests (never shrinks; capacity <= 2^31). Synchronous. */
+int sha1chunk_index_reserve(sha1chunk_index *ix, size_t capacity);
+size_t sha1chunk_index_capacity(const sha1chunk_index *ix); /* 0 for NULL */
+
+/* Digest i of the call gets position size_before + i.  Where d_skip is not NULL and
+ * d_skip[i] != 0, the position is used up but the digest is NOT admitted: no lookup
+ * ever answers it.  Device arrays, asynchronous on `stream`; never waits for the
+ * device and never allocates (SHA1CHUNK_EINVAL when size + k > capacity). */
+int sha1chunk_index_append_device_async(sha1chunk_index *ix, const uint8_t *d_digests, size_t k,
+                                        const uint8_t *d_skip, void *stream);
+/* The same for host arrays; synchronous; grows the index when it is full. */
+int sha1chunk_index_append(sha1chunk_index *ix, const uint8_t *digests, size_t k,
+                           const uint8_t *skip);
 
 /* ids[i] = lowest position p with table[p] == digests[i], else SHA1CHUNK_NO_MATCH.
  * Device arrays, asynchronous on `stream`; never waits for the device. */
@@ -705,6 +793,11 @@ int sha1chunk_index_lookup(const sha1chunk_index *ix, const uint8_t *digests, si
 /* Hash, then look up: the arguments of sha1chunk_hash_batch, ids instead of digests. */
 int sha1chunk_match_batch(const sha1chunk_index *ix, const void *base, const uint64_t *offsets,
                           const uint32_t *lengths, size_t n, uint32_t *ids, unsigned flags);
+/* The arguments of sha1chunk_verify_batch: verify, then append every digest
+ * (skip = mismatch), so that exactly the verified chunks join the set. */
+int sha1chunk_admit_batch(sha1chunk_index *ix, const void *base, const uint64_t *offsets,
+                          const uint32_t *lengths, size_t n, const uint8_t *expected,
+                          uint8_t *mismatch, unsigned flags);
 /* The arguments of sha1chunk_hash_fd, ids instead of digests. */
 long sha1chunk_match_fd(const sha1chunk_index *ix, int fd, uint32_t *ids, size_t max_chunks,
                         size_t *total_chunks);
